@@ -134,6 +134,36 @@ def output_check(gan, batch, precision, img, mask):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000     # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: write `arrays` (name -> numpy array) as <dirname>/<name>.npy in float32, at most `budget` bytes in all.
+    Smallest array first, an array is written whole if it fits in what is left after a quarter of the rest is set aside for
+    each array still to come; otherwise the file holds a fixed sample of its elements in flat order: the sorted positions
+    np.random.default_rng(seed).choice(size, k, replace=False), the same in every run with the same shapes.  Returns what
+    was written, for the JSON line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left = budget // 4 - 64 * len(arrays)          # float32 elements, less a .npy header per file
+    done = {}
+    order = sorted(arrays, key=lambda k: arrays[k].size)
+    for i, name in enumerate(order):
+        a = np.ascontiguousarray(arrays[name])
+        to_come = len(order) - i - 1
+        if a.size <= left - to_come * (left // 4):
+            out, how = a.astype(np.float32), "whole"
+        else:
+            k = left // (to_come + 1)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, k, replace=False))
+            out, how = a.reshape(-1)[idx].astype(np.float32), "sample of %d elements in flat order, positions: sorted " \
+                "np.random.default_rng(%d).choice(%d, %d, replace=False)" % (k, seed, a.size, k)
+        np.save(os.path.join(dirname, name + ".npy"), out)
+        left -= out.size
+        done[name] = {"shape": list(a.shape), "dtype": str(a.dtype), "saved": how}
+    return {"dir": dirname, "arrays": done}
+
+
 def measure_secondary(gan, batch, precision, steps, warmup, dev, graph=False):
     """A short, separate measurement of another BASELINE.json configuration (own model, own context), reported under
     `secondary` -- the headline fields stay those of configs[1].  graph=True: the step is captured into a hipGraph during
@@ -490,8 +520,9 @@ def main():
     ap.add_argument("--settle-steps", type=int, default=80,
                     help="untimed steps in front of the warm-up (default 80 = half a second at FFHQ batch 8): an idle MI355X needs a few tenths of a "
                          "second of load before its clocks settle -- without them the first one or two timed regions read 3 %% low (the same count on every rank)")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps each, back to back after ONE warm-up; value = their median, every region is printed (runs)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed regions of --steps steps each, back to back after ONE warm-up (default 1: --steps is the number of timed "
+                         "steps); value = their median, every region is printed (runs)")
     ap.add_argument("--gan", default="ffhq", choices=("ffhq", "cars", "bedrooms"))
     ap.add_argument("--batch", type=int, default=8, help="samples per GPU per step")
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"),
@@ -507,6 +538,9 @@ def main():
     ap.add_argument("--stub-producer", action="store_true",
                     help="CPU rehearsal of the N-rank control flow: gloo, deterministic uint8 pairs instead of the kernels "
                          "(the line says data: stub and is not a measurement)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to its caller (rank 0: the gathered image and mask "
+                         "of every rank) as DIR/image.npy and DIR/mask.npy, float32, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
     t_proc = time.perf_counter()
 
@@ -553,6 +587,11 @@ def main():
         loop = TimedLoop(producer, gat, world, dev, args.allow_blocking)
         timing = loop.run(args.settle_steps + args.warmup, args.steps, args.repeats)
         dt = median([loop.max_over_ranks(d) for d in timing["dts_local"]])
+        dumped = None
+        if rank == 0 and args.dump_outputs and timing["gather"] != "blocking":
+            parts = gat.result(timing["last_slot"])
+            dumped = dump_outputs(args.dump_outputs, {"image": torch.cat([p[0] for p in parts]).numpy(),
+                                                      "mask": torch.cat([p[1] for p in parts]).numpy()})
         if rank == 0:
             # content and order of the last gathered batch: rank r's row must hold rank r's pairs of the last step
             ok = True
@@ -570,7 +609,7 @@ def main():
                 "config": {"workload": "stub producer %dx%dx%d u8 pairs, batch=%d per rank" % (R, R, nch, B),
                            "global_batch": world * B, "parallelism": "dp%d" % world, "gather": timing["gather"],
                            "backend": dist.get_backend() if ranks > 1 else "none"},
-                "gathered_matches_producers": ok}), flush=True)
+                "gathered_matches_producers": ok, "dump_outputs": dumped}), flush=True)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -603,6 +642,13 @@ def main():
     # ~130 launches of a step cost ~5 % of the step)
     timing = loop.run(args.settle_steps + args.warmup, args.steps, args.repeats)
     t_warm, state, last_slot = timing["warmup_s"], {"gather": timing["gather"]}, timing["last_slot"]
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step handed its caller: the pairs of every rank, gathered on rank 0 in global sample order
+        # (the blocking fallback keeps no buffer: rank 0's own batch is computed once more from the same inputs)
+        parts = gat.result(last_slot) if state["gather"] != "blocking" else [gen.generate_batch(z, noise)]
+        dumped = dump_outputs(args.dump_outputs, {"image": torch.cat([p[0] for p in parts]).cpu().numpy(),
+                                                  "mask": torch.cat([p[1] for p in parts]).cpu().numpy()})
     # ---- roofline pass (untimed): the same K steps with every launch bracketed by HIP events on its
     # stream, and with the decoder/synthesis stream overlap off, so that a kernel's duration is its own
     # and not stretched by the kernel running beside it
@@ -721,6 +767,8 @@ def main():
             out["cpu_baseline"] = cpu_baseline(args.gan)
             wall["cpu_baseline"] = round(time.perf_counter() - t1, 2)
         out["wall_s"] = wall
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

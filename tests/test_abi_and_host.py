@@ -228,9 +228,12 @@ def test_dataset_writer_withholds_the_files_of_a_batch_whose_device_check_failed
     w.submit(img, mask, 2, status=[torch.zeros(2, dtype=torch.int32), torch.zeros(2, dtype=torch.int32)])      # two replicas, both clean
     assert w.drain() == 4
     w.submit(img, mask, 4, status=[torch.tensor([0, 0], dtype=torch.int32), torch.tensor([1, 0], dtype=torch.int32)])   # one replica's statistics word set
-    w.submit(img, mask, 6, status=[torch.zeros(2, dtype=torch.int32)])                                         # later batch: halted too
     with pytest.raises(DeviceCheckFailed) as e:
-        w.close()
+        # later batch: halted too -- refused by submit() itself once the dispatcher has already seen batch 4, else by close()
+        try:
+            w.submit(img, mask, 6, status=[torch.zeros(2, dtype=torch.int32)])
+        finally:
+            w.close()
     assert e.value.first_index == 4 and "global sample index 4" in str(e.value) and "instance-norm statistic" in str(e.value)
     names = sorted(os.listdir(tmp_path))
     assert names == sorted(["img_%06d.jpg" % i for i in range(4)] + ["mask_%06d.png" % i for i in range(4)])
@@ -514,6 +517,41 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks():
     assert line["config"]["gather"] == "overlapped" and line["config"]["backend"] == "gloo"
     assert line["launcher"].startswith("self-launched") and line["data"] == "stub"
     assert line["gathered_matches_producers"] is True and line["steps"] == 3 and line["config"]["global_batch"] == 4
+
+
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes what the last timed step handed it (the gathered pairs of both ranks, global sample
+    order) as float32 .npy; --steps alone sets the timed steps (one region by default)."""
+    import bench
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub-producer", "--steps", "3",
+                          "--warmup", "2", "--settle-steps", "4", "--batch", "2", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=300, env=_bench_env())
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    line = _one_json_line(out.stdout)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["image.npy", "mask.npy"]
+    last = [bench.StubProducer(r, 2, 32, 3).pairs(4 + 2 + 3 - 1) for r in range(2)]
+    for i, name in enumerate(("image", "mask")):
+        a = np.load(str(tmp_path / (name + ".npy")))
+        assert a.dtype == np.float32 and line["dump_outputs"]["arrays"][name]["saved"] == "whole"
+        assert np.array_equal(a, np.concatenate([p[i].numpy() for p in last]).astype(np.float32))
+
+
+def test_bench_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """An output too large for the budget is replaced by the same seeded sample in every run; the files stay within it."""
+    import bench
+    g = np.random.default_rng(5)
+    arrays = {"image": g.integers(0, 256, (4, 64, 64, 3), dtype=np.uint8), "mask": g.integers(0, 2, (4, 64, 64), dtype=np.uint8)}
+    budget = 4 * 30000
+    for d in ("a", "b"):
+        r = bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= budget
+    assert r["arrays"]["mask"]["saved"] == "whole" and r["arrays"]["image"]["saved"].startswith("sample")
+    for name in arrays:
+        assert np.array_equal(np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy"))))
+    img = np.load(str(tmp_path / "a" / "image.npy"))
+    idx = np.sort(np.random.default_rng(0).choice(arrays["image"].size, img.size, replace=False))
+    assert np.array_equal(img, arrays["image"].reshape(-1)[idx].astype(np.float32))
 
 
 def test_bench_under_torchrun_is_unchanged_and_a_dead_rank_fails_the_run():
