@@ -14,6 +14,7 @@
 //   adam_kernel         mx.optimizer.Adam                                                     seg_solver.py:203-219
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
@@ -483,7 +484,10 @@ __device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, uns
     }
 }
 
-__global__ __launch_bounds__(256) void dropout_mask_kernel(long total, unsigned long long seed, unsigned stream_id, float keep, uint8_t* mask) {
+// keep iff the uniform ((c >> 8) + 0.5) * 2^-24 < keep_prob, compared exactly as the integer (c >> 8) < kept (the host's
+// threshold): forming the uniform in fp32 rounds (c >> 8) + 0.5 for c >> 8 >= 2^23, so 0xFFFFFF became 1.0 and was dropped
+// even at keep_prob = 1
+__global__ __launch_bounds__(256) void dropout_mask_kernel(long total, unsigned long long seed, unsigned stream_id, unsigned kept, uint8_t* mask) {
     const long quads = (total + 3) / 4;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < quads; q += (long)gridDim.x * 256) {
         unsigned c[4] = {(unsigned)q, (unsigned)(q >> 32), stream_id, 0x44524F50u /* "DROP" */};
@@ -491,7 +495,7 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(long total, unsigned 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const long i = 4 * q + j;
-            if (i < total) mask[i] = (((float)(c[j] >> 8) + 0.5f) * 5.9604644775390625e-8f) < keep ? 1 : 0;
+            if (i < total) mask[i] = (c[j] >> 8) < kept ? 1 : 0;
         }
     }
 }
@@ -699,8 +703,10 @@ int gsa_train_add(void* stream, int64_t count, const float* a, const float* b, f
 
 int gsa_train_dropout_mask(void* stream, int64_t count, uint64_t seed, uint32_t stream_id, float keep_prob, uint8_t* mask) {
     if (count <= 0 || !mask || !(keep_prob > 0.0f && keep_prob <= 1.0f)) return GSA_ERR_INVALID_;
+    // (x + 0.5) * 2^-24 < keep  <=>  x < keep * 2^24 - 0.5  <=>  x < ceil(keep * 2^24 - 0.5)   (exact in double; 2^24 at keep 1)
+    const unsigned kept = (unsigned)ceil((double)keep_prob * 16777216.0 - 0.5);
     hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for((count + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (long)count,
-                       (unsigned long long)seed, stream_id, keep_prob, mask);
+                       (unsigned long long)seed, stream_id, kept, mask);
     TRY_HIP(hipGetLastError());
     return GSA_OK_;
 }

@@ -90,7 +90,8 @@ int gsa_train_upsample2_bwd(void* stream, int32_t n, int32_t C, int32_t Hs, int3
 /* out = a + b (residual add and gradient accumulation), count elements; out may alias a. */
 int gsa_train_add(void* stream, int64_t count, const float* a, const float* b, float* out);
 
-/* Dropout keep mask: mask[i] = uniform(seed, stream_id, i) < keep_prob, Philox4x32-10 counter = (i/4, stream_id). */
+/* Dropout keep mask: mask[i] = uniform(seed, stream_id, i) < keep_prob, Philox4x32-10 counter = (i/4, stream_id), with
+ * uniform = ((word >> 8) + 0.5) * 2^-24 compared exactly (so keep_prob = 1 keeps every element). */
 int gsa_train_dropout_mask(void* stream, int64_t count, uint64_t seed, uint32_t stream_id, float keep_prob, uint8_t* mask);
 
 /* MXNet's Adam update (optimizer 'adam', seg_solver.py:203-219):  g' = g*rescale + wd*w;  m = b1*m+(1-b1)*g';

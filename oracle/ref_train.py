@@ -2,7 +2,7 @@
 
 The decoder of reference networks_seg.py:49-113 in training mode (BatchNorm batch statistics, explicit Dropout keep
 masks so that the device path can be compared sample for sample), the weighted SoftmaxCELoss of
-seg_solver.py:395-407, ``backward()`` and MXNet's Adam update.  CPU, float32."""
+seg_solver.py:395-407, ``backward()`` and MXNet's Adam update.  CPU, float32 (or float64 where a test asks for it)."""
 import math
 
 import numpy as np
@@ -46,11 +46,12 @@ def forward_train(cfg, p, feats, masks, keep=0.5):
             return F.conv2d(inp, p[fn + ".weight"], p[fn + ".bias"], padding=1), running
 
 
-def train_step(cfg, params, feats, labels, masks, t, m, v, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, keep=0.5):
-    """One step on copies: -> (loss per sample, new params, new m, new v).  ``t`` = step count after this step."""
-    p = {k: torch.tensor(np.asarray(a, np.float32), requires_grad=not k.endswith(("running_mean", "running_var")))
+def train_step(cfg, params, feats, labels, masks, t, m, v, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, keep=0.5, dtype=np.float32):
+    """One step on copies: -> (loss per sample, new params, new m, new v, raw gradients).  ``t`` = step count after this
+    step; ``dtype``: the precision of the whole step (the inputs are rounded to fp32 first either way)."""
+    p = {k: torch.tensor(np.asarray(a, np.float32).astype(dtype), requires_grad=not k.endswith(("running_mean", "running_var")))
          for k, a in params.items()}
-    feats = [torch.tensor(np.asarray(f, np.float32)) for f in feats]
+    feats = [torch.tensor(np.asarray(f, np.float32).astype(dtype)) for f in feats]
     labels = torch.tensor(np.asarray(labels)).long()
     n = feats[0].shape[0]
     logits, running = forward_train(cfg, p, feats, [None if mk is None else torch.tensor(np.asarray(mk)) for mk in masks], keep)
@@ -64,8 +65,8 @@ def train_step(cfg, params, feats, labels, masks, t, m, v, lr=1e-4, b1=0.9, b2=0
             new_p[k] = running[k].numpy()
             continue
         g = (w.grad if w.grad is not None else torch.zeros_like(w)) / n
-        mm = b1 * torch.tensor(m[k]) + (1 - b1) * g
-        vv = b2 * torch.tensor(v[k]) + (1 - b2) * g * g
+        mm = b1 * torch.tensor(np.asarray(m[k], dtype)) + (1 - b1) * g
+        vv = b2 * torch.tensor(np.asarray(v[k], dtype)) + (1 - b2) * g * g
         new_m[k], new_v[k] = mm.numpy(), vv.numpy()
         new_p[k] = (w.detach() - lr_t * mm / (vv.sqrt() + eps)).numpy()
     return per_sample.detach().numpy(), new_p, new_m, new_v, {k: (w.grad.numpy() if w.grad is not None else None) for k, w in p.items() if w.requires_grad}

@@ -85,6 +85,47 @@ def test_gradients_match_autograd_directly(features, start_res):
         assert np.abs(got - gref).max() <= 2e-3 * scale + 1e-6, "%s: %.3e of %.3e" % (k, np.abs(got - gref).max(), scale)
 
 
+C_TRAIN = 2e-2
+
+
+def test_gradients_match_float64_autograd_at_cars_size():
+    """The raw gradients of one step of the cars decoder (max_res_log2 9: 512^2 output, batch 1, the real channel counts)
+    against oracle/ref_train.py in float64, element by element per tensor: |got - ref| <= C_TRAIN * (|ref| + rms(ref)).
+    A bias in front of BatchNorm has an exactly-zero gradient: its fp32 value is rounding noise, bounded by C_TRAIN *
+    rms of the weight gradient of the same convolution.  Through eight BatchNorm levels (the lowest one over 16 pixels)
+    fp32 rounding alone reaches a few 1e-3 here: torch's own float32 CPU evaluation of this decoder is off by up to
+    1.5e-3 * (|ref| + rms(ref)); measured on an MI355X: 1.03e-2 (one element of main_block_1.1.base_layers.0.weight, at
+    16 px), 3.5e-3 on cvt_block_0.0.weight; C_TRAIN is about twice the worst."""
+    from gan_segmentation_amd import weights as W
+    from gan_segmentation_amd.trainer import DecoderTrainer
+    from oracle import ref_train
+    dcfg = W.decoder_config(W.GAN_MAX_RES_LOG2["cars"])
+    chans = dcfg["in_channels"]
+    dp = W.synthetic_decoder_params(dcfg, seed=9)
+    rng = np.random.default_rng(5)
+    feats = [rng.standard_normal((1, c, 4 << i, 4 << i)).astype(np.float32) for i, c in enumerate(chans)]
+    R = 4 << (len(chans) - 1)
+    assert R == 512
+    labels = rng.integers(-1, 2, (1, R, R)).astype(np.int64)
+    tr = DecoderTrainer(dcfg, dp, lr=0.0, seed=3)
+    masks = tr.dropout_masks([(1, dcfg["features"][i], 4 << i, 4 << i) for i in range(len(chans))])
+    tr.step(feats, labels, masks=masks)
+    zeros = {k: np.zeros_like(v) for k, v in dp.items()}
+    _ps, _p, _m, _v, grads = ref_train.train_step(dcfg, dp, feats, labels, [mk.cpu().numpy() for mk in masks], 1, zeros, zeros,
+                                                  lr=0.0, dtype=np.float64)
+    worst = 0.0
+    for k, gref in grads.items():
+        got = tr.g[k].cpu().numpy().astype(np.float64)
+        if k.endswith(".bias") and ("cvt_block" in k or "base_layers" in k):
+            bound = np.sqrt(np.mean(grads[k[:-len("bias")] + "weight"] ** 2))
+        else:
+            bound = np.abs(gref) + np.sqrt(np.mean(gref ** 2))
+        ratio = np.abs(got - gref) / (C_TRAIN * bound)
+        assert ratio.max() <= 1.0, "%s: %d elements outside, worst ratio %.3f" % (k, int((ratio > 1).sum()), ratio.max())
+        worst = max(worst, float(ratio.max()))
+    print("worst |got - ref| / (C_TRAIN * bound): %.4f" % worst)
+
+
 def test_sync_batchnorm_two_ranks_equal_the_joint_batch():
     """cfg['use_sync_bn'] (reference networks_seg.py:20-21,30-31,73-74): two ranks with one sample each, exchanging the
     BatchNorm sums and the gradients, must compute what ONE trainer computes on the two-sample batch.  The ranks are two
