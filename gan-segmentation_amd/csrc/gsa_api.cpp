@@ -59,7 +59,9 @@ struct DecLevelDev {
 };
 
 struct ProfEntry {
-    std::string name;
+    const void* kern = nullptr;   // the kernel launched
+    std::string layer;            // profile level 2: the layer it ran for
+    std::string name;             // "<kernel signature>[ | <layer>]", filled by gsa_profile_collect
     double ms = 0, flops = 0, bytes = 0, alg_flops = 0;   // flops: executed by the kernel; alg_flops: of the reference's formulation
     int64_t launches = 0;
 };
@@ -136,6 +138,8 @@ struct gsa_ctx {
     std::vector<ProfEntry> prof_entries;
     std::vector<ProfEvent> prof_events;
     std::vector<hipEvent_t> event_pool;
+    std::map<const void*, std::string> kernel_names;   // resolved once per kernel by gsa_profile_collect
+    int prof_multi = 0;           // Launch scopes that launched more than one kernel (a bug: gsa_profile_collect reports it)
 };
 
 namespace {
@@ -446,45 +450,42 @@ void reset_generator_dev(gsa_ctx* c) {
 
 // ---------------------------------------------------------------- profiling wrapper
 
+// Brackets ONE kernel launch: its label is the kernel the launch helper (gsa_kernels.h) records, the layer, and the FLOP / byte
+// figures given here.  A scope that launched nothing (a launch the diagnostic build skips) records no entry.
 struct Launch {
     gsa_ctx* c;
     hipStream_t s;
-    int entry = -1;
-    hipEvent_t a = nullptr, b = nullptr;
-    std::string kname_s;
-    const char* kname = "";
-    const char* label = nullptr;
+    const char* label;
+    double flops, bytes, alg;
+    std::string entry_layer;      // profile level 2: the layer part of the entry's key
+    hipEvent_t a = nullptr;
     // flops = FLOP the kernel executes; alg = FLOP of the same layer in the reference's formulation (2*MACs of the direct
     // 9-tap / 16-tap convolution) when the kernel uses a cheaper form (sub-pixel, Winograd); < 0: the same
-    Launch(gsa_ctx* ctx, hipStream_t st, const char* kernel, const char* layer, double flops, double bytes, double alg = -1.0) : c(ctx), s(st) {
-        kname_s = kernel; kname = kname_s.c_str(); label = layer;
+    Launch(gsa_ctx* ctx, hipStream_t st, const char* layer, double flops_, double bytes_, double alg_ = -1.0)
+        : c(ctx), s(st), label(layer), flops(flops_), bytes(bytes_), alg(alg_ < 0 ? flops_ : alg_) {
+        (void)take_launch_record();
         if (!c->prof) return;
-        std::string key = kernel;
-        if (c->prof > 1 && layer) { key += " | "; key += layer; }
-        for (size_t i = 0; i < c->prof_entries.size(); ++i)
-            if (c->prof_entries[i].name == key) { entry = (int)i; break; }
-        if (entry < 0) {
-            ProfEntry e;
-            e.name = key;
-            c->prof_entries.push_back(e);
-            entry = (int)c->prof_entries.size() - 1;
-        }
-        c->prof_entries[entry].flops += flops;
-        c->prof_entries[entry].alg_flops += alg < 0 ? flops : alg;
+        if (c->prof > 1 && layer) entry_layer = layer;
         // bf16 mode: the activation tensors are 2 bytes per element (the fp32 noise planes and the parameters are a few per cent)
-        c->prof_entries[entry].bytes += (c->bf16 && layer && strncmp(layer, "g.mapping", 9) && strncmp(layer, "g.styles", 8) && !strstr(layer, "finalize")) ? 0.5 * bytes : bytes;
-        c->prof_entries[entry].launches += 1;
-        auto get = [&]() {
-            hipEvent_t e = nullptr;
-            if (!c->event_pool.empty()) { e = c->event_pool.back(); c->event_pool.pop_back(); }
-            else (void)hipEventCreate(&e);
-            return e;
-        };
-        a = get(); b = get();
+        if (c->bf16 && layer && strncmp(layer, "g.mapping", 9) && strncmp(layer, "g.styles", 8) && !strstr(layer, "finalize")) bytes *= 0.5;
+        a = event();
         (void)hipEventRecord(a, s);
     }
+    hipEvent_t event() {
+        if (c->event_pool.empty()) {
+            hipEvent_t e = nullptr;
+            (void)hipEventCreate(&e);
+            return e;
+        }
+        hipEvent_t e = c->event_pool.back();
+        c->event_pool.pop_back();
+        return e;
+    }
     ~Launch() {
+        const LaunchRecord r = take_launch_record();
 #ifdef GSA_STAMP
+        const std::string kname_s = r.count == 1 ? kernel_name(r.kern) : std::string();
+        const char* kname = kname_s.c_str();
         if (c->stamps && label && (strstr(kname, "conv") || strstr(kname, "subpixel"))) {   // diagnostic build: per-phase wave-cycle sums
             (void)hipStreamSynchronize(s);
             unsigned long long h[16];
@@ -507,13 +508,32 @@ struct Launch {
             }
         }
 #endif
-        if (entry < 0) return;
+        if (!a) return;
+        if (r.count != 1) {
+            c->event_pool.push_back(a);
+            if (r.count > 1) ++c->prof_multi;
+            return;
+        }
+        int entry = -1;
+        for (size_t i = 0; i < c->prof_entries.size() && entry < 0; ++i)
+            if (c->prof_entries[i].kern == r.kern && c->prof_entries[i].layer == entry_layer) entry = (int)i;
+        if (entry < 0) {
+            ProfEntry e;
+            e.kern = r.kern;
+            e.layer = entry_layer;
+            c->prof_entries.push_back(e);
+            entry = (int)c->prof_entries.size() - 1;
+        }
+        ProfEntry& e = c->prof_entries[entry];
+        e.flops += flops;
+        e.alg_flops += alg;
+        e.bytes += bytes;
+        e.launches += 1;
+        hipEvent_t b = event();
         (void)hipEventRecord(b, s);
         c->prof_events.push_back(ProfEvent{a, b, entry});
     }
 };
-
-const char* conv_kernel_name(const ConvParams& cp, int n, int epi, bool sc) { return conv3x3_kernel_name(cp, epi, sc, n); }
 
 }  // namespace
 
@@ -1024,19 +1044,19 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
     // mapping network: PixelNorm, 8 x (dense + LeakyReLU)
     int cur = 0;
     if (mapping_fused(L, c->device)) {
-        Launch lp(c, s, "mapping_kernel", "g.mapping", 3.0 * N * L + 16.0 * N * L * L, 4.0 * (8.0 * L * (double)L + 18 * N * L));
+        Launch lp(c, s, "g.mapping", 3.0 * N * L + 16.0 * N * L * L, 4.0 * (8.0 * L * (double)L + 18 * N * L));
         HIP_TRY(launch_mapping(z, c->map_wt, c->map_b, c->map_ll, c->lat[0], c->map_ctl, n, L, c->device, s, c->fault == 1 ? 1 : 0));
     } else {
-        { Launch lp(c, s, "pixelnorm_kernel", "g.mapping.pixelnorm", 3.0 * N * L, 8.0 * N * L);
+        { Launch lp(c, s, "g.mapping.pixelnorm", 3.0 * N * L, 8.0 * N * L);
           HIP_TRY(launch_pixelnorm(z, c->lat[0], n, L, s)); }
         for (int i = 0; i < 8; ++i) {
-            Launch lp(c, s, "dense_kernel", "g.mapping.dense", 2.0 * N * L * L, 4.0 * (L * (double)L + 2 * N * L));
+            Launch lp(c, s, "g.mapping.dense", 2.0 * N * L * L, 4.0 * (L * (double)L + 2 * N * L));
             HIP_TRY(launch_dense(c->lat[cur], c->map_wt[i], c->map_b[i], c->lat[cur ^ 1], n, L, L, 1, s));
             cur ^= 1;
         }
     }
     const float* w = c->lat[cur];
-    { Launch lp(c, s, "styles_kernel", "g.styles", 2.0 * N * L * c->style_cols, 4.0 * ((double)L * c->style_cols + N * c->style_cols));
+    { Launch lp(c, s, "g.styles", 2.0 * N * L * c->style_cols, 4.0 * ((double)L * c->style_cols + N * c->style_cols));
       HIP_TRY(launch_styles(w, c->latent_avg, c->psi, c->style_wt, c->style_b, c->style_col_layer, c->styles, n, L, c->style_cols, s)); }
 
     char layer[64];
@@ -1062,16 +1082,14 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
                     if (B.is_deconv || R >= 16) {
                         // Deconvolution 4x4 s2, or nearest-x2 + conv3x3 in sub-pixel form (same kernel)
                         snprintf(layer, sizeof layer, B.is_deconv ? "g.%d.deconv_1" : "g.%d.conv_1", R);
-                        static thread_local char kn[128];
-                        snprintf(kn, sizeof kn, "%s", subpixel_kernel_name(cp, EPI_RAW, false, n));
                         // executed: 4 taps per output, or 9 products per 2x2 class outputs in the Winograd F(2x2,2x2) form; algorithmic: the
                         // reference's operator (16-tap transposed conv = 4 taps per output; 9-tap conv on the upsampled image)
-                        Launch lp(c, s, kn, layer, 2.0 * px * C * Cin * (subpixel_uses_wino(cp) ? 2.25 : 4.0), 4.0 * (px / 4 * Cin + px * C), 2.0 * px * C * Cin * (B.is_deconv ? 4 : 9));
+                        Launch lp(c, s, layer, 2.0 * px * C * Cin * (subpixel_uses_wino(cp) ? 2.25 : 4.0), 4.0 * (px / 4 * Cin + px * C), 2.0 * px * C * Cin * (B.is_deconv ? 4 : 9));
                         HIP_TRY(launch_subpixel(cp, EPI_RAW, false, n, s));
                     } else {
                         cp.up = 1;
                         snprintf(layer, sizeof layer, "g.%d.conv_1", R);
-                        Launch lp(c, s, conv_kernel_name(cp, n, EPI_RAW, false), layer, 2.0 * px * C * Cin * 9, 4.0 * (px / 4 * Cin + px * C));
+                        Launch lp(c, s, layer, 2.0 * px * C * Cin * 9, 4.0 * (px / 4 * Cin + px * C));
                         HIP_TRY(launch_conv3x3(cp, EPI_RAW, false, n, s));
                     }
                     pp.src = c->t_raw; pp.src_per_sample = 1; pp.blur = B.blur;
@@ -1084,11 +1102,11 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
                     fp.gamma = B.gamma[0]; fp.beta = B.beta[0];
                     fp.aff = c->aff1;
                     fp.flags = c->map_ctl;
-                    Launch lp(c, s, pp.blur ? "post_fin_kernel<blur>" : "post_fin_kernel<const>", layer, 0.0, 4.0 * (2 * px * C + px));
+                    Launch lp(c, s, layer, 0.0, 4.0 * (2 * px * C + px));
                     HIP_TRY(launch_post_fin(pp, fp, n, s));
                     continue;
                 }
-                Launch lp(c, s, pp.blur ? "post_kernel<blur>" : "post_kernel<const>", layer, 0.0, 4.0 * (2 * px * C + px));
+                Launch lp(c, s, layer, 0.0, 4.0 * (2 * px * C + px));
 #ifdef GSA_DBG_HOOKS
                 // diagnostic build only (`make dbg`, GSA_DBG bit 3; WRONG results): leave out the blur / noise / bias / LeakyReLU / statistics
                 // pass of the 512^2 and 1024^2 levels -- what fusing it into the stride-2 convolution could win AT MOST, measured on the
@@ -1111,7 +1129,7 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
                     cp.fin_style = c->styles + B.style_off[1]; cp.fin_style_stride = c->style_cols;
                     cp.fin_gamma = B.gamma[1]; cp.fin_beta = B.beta[1]; cp.fin_aff = c->aff2[l]; cp.fin_flags = c->map_ctl;
                 }
-                Launch lp(c, s, conv_kernel_name(cp, n, EPI_SYNTH, false), layer, 2.0 * px * C * C * (conv_uses_wino43(cp, EPI_SYNTH, false) ? 2.25 : conv_uses_wino(cp, EPI_SYNTH, false) ? 4 : 9), 4.0 * (2 * px * C + px), 2.0 * px * C * C * 9);
+                Launch lp(c, s, layer, 2.0 * px * C * C * (conv_uses_wino43(cp, EPI_SYNTH, false) ? 2.25 : conv_uses_wino(cp, EPI_SYNTH, false) ? 4 : 9), 4.0 * (2 * px * C + px), 2.0 * px * C * C * 9);
                 HIP_TRY(launch_conv3x3(cp, EPI_SYNTH, false, n, s));
                 prow = rows;
                 if (fused_fin) continue;
@@ -1133,20 +1151,20 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
             if ((c->dbg & 32) && ((k == 0 && R <= 32) || (k == 1 && R <= 8))) continue;
             if ((c->dbg & 64)) continue;      // bit 6: without ANY finalize launch (the bound of every such fusion)
 #endif
-            Launch lp(c, s, "finalize_kernel", layer, 0.0, 16.0 * N * prow * C);
+            Launch lp(c, s, layer, 0.0, 16.0 * N * prow * C);
             HIP_TRY(launch_finalize(fp, n, s));
         }
         if (record_levels) HIP_TRY(hipEventRecord(c->ev_level[l], s));   // feature l (x2, aff2) is complete
         if (feats && feats[l]) {
             snprintf(layer, sizeof layer, "g.%d.export", R);
-            Launch lp(c, s, "export_nchw_kernel", layer, 0.0, 8.0 * px * C);
+            Launch lp(c, s, layer, 0.0, 8.0 * px * C);
             HIP_TRY(launch_export_nchw(c->x2[l], c->aff2[l], feats[l], n, R, R, C, c->bf16, s));
         }
     }
     if (rgb || img) {
         const int l = nlev - 1, R = c->blk[l].R, C = c->blk[l].C, nc = c->gc.channels;
         const double px = N * R * R;
-        Launch lp(c, s, C <= 16 ? "torgb_direct_kernel" : "torgb_kernel", "g.torgb", 2.0 * px * C * nc, px * (4.0 * C + (rgb ? 4.0 * nc : 0) + (img ? nc : 0)));
+        Launch lp(c, s, "g.torgb", 2.0 * px * C * nc, px * (4.0 * C + (rgb ? 4.0 * nc : 0) + (img ? nc : 0)));
         HIP_TRY(launch_torgb(c->x2[l], c->aff2[l], c->rgb_w, c->rgb_b, rgb, img, n, R, R, C, nc, c->bf16, s));
     }
     return GSA_OK;
@@ -1184,7 +1202,7 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
             const int nc = c->gc.channels;
             if (with_rgb) { cp.rgb_w = c->rgb_w; cp.rgb_b = c->rgb_b; cp.rgb_img = rgb_img; }
             snprintf(layer, sizeof layer, with_rgb ? "d.cvt_%d+torgb" : "d.cvt_%d", i);
-            Launch lp(c, s, conv_kernel_name(cp, n, EPI_DEC, false), layer,
+            Launch lp(c, s, layer,
                       2.0 * px * d.F * d.I * (conv_uses_wino43(cp, EPI_DEC, false) ? 2.25 : conv_uses_wino(cp, EPI_DEC, false) ? 4 : 9) + (with_rgb ? 2.0 * px * d.I * nc : 0.0),
                       4.0 * px * (d.I + d.F) + (with_rgb ? px * nc : 0.0), 2.0 * px * d.F * d.I * 9 + (with_rgb ? 2.0 * px * d.I * nc : 0.0));
             HIP_TRY(launch_conv3x3(cp, EPI_DEC, false, n, s));
@@ -1202,14 +1220,12 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
                 if (d.has_sc) { cp.wsc = d.sc_w; cp.sc_bias = d.sc_b; cp.out_sc = c->scb[i]; }
                 snprintf(layer, sizeof layer, "d.main_%d.a", i);
                 if (R2 >= 16) {   // sub-pixel form: 4 taps per output instead of 9
-                    static thread_local char kn[128];
-                    snprintf(kn, sizeof kn, "%s", subpixel_kernel_name(cp, EPI_DEC, d.has_sc, n));
-                    Launch lp(c, s, kn, layer, 2.0 * px2 * d.cs * d.in_c * (subpixel_uses_wino(cp) ? 2.25 : 4.0) + (d.has_sc ? 2.0 * px * d.cs * d.in_c : 0.0),
+                    Launch lp(c, s, layer, 2.0 * px2 * d.cs * d.in_c * (subpixel_uses_wino(cp) ? 2.25 : 4.0) + (d.has_sc ? 2.0 * px * d.cs * d.in_c : 0.0),
                               4.0 * (px * d.in_c + px2 * d.cs + (d.has_sc ? px * d.cs : 0.0)), 2.0 * px2 * d.cs * d.in_c * (9 + (d.has_sc ? 1 : 0)));
                     cp.up = 0;
                     HIP_TRY(launch_subpixel(cp, EPI_DEC, d.has_sc, n, s));
                 } else {
-                    Launch lp(c, s, conv_kernel_name(cp, n, EPI_DEC, d.has_sc), layer,
+                    Launch lp(c, s, layer,
                               2.0 * px2 * d.cs * d.in_c * (9 + (d.has_sc ? 1 : 0)), 4.0 * (px * d.in_c + px2 * d.cs * (d.has_sc ? 2 : 1)));
                     HIP_TRY(launch_conv3x3(cp, EPI_DEC, d.has_sc, n, s));
                 }
@@ -1224,12 +1240,12 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
                 else if (i == s0) { cp.resid = c->cvt[i]; cp.resid_up = 1; }   // identity shortcut: the upsampled input itself
                 else { cp.resid = c->prev[i - 1]; cp.resid1 = c->cvt[i]; cp.res_c0 = d.F; cp.resid_up = 1; }   // ... over concat(prev, cvt)
                 snprintf(layer, sizeof layer, "d.main_%d.b", i);
-                Launch lp(c, s, conv_kernel_name(cp, n, EPI_DEC, false), layer, 2.0 * px2 * d.cs * d.cs * (conv_uses_wino43(cp, EPI_DEC, false) ? 2.25 : conv_uses_wino(cp, EPI_DEC, false) ? 4 : 9), 4.0 * px2 * d.cs * 3, 2.0 * px2 * d.cs * d.cs * 9);
+                Launch lp(c, s, layer, 2.0 * px2 * d.cs * d.cs * (conv_uses_wino43(cp, EPI_DEC, false) ? 2.25 : conv_uses_wino(cp, EPI_DEC, false) ? 4 : 9), 4.0 * px2 * d.cs * 3, 2.0 * px2 * d.cs * d.cs * 9);
                 HIP_TRY(launch_conv3x3(cp, EPI_DEC, false, n, s));
             }
         } else {
             snprintf(layer, sizeof layer, "d.final_%d", i);
-            Launch lp(c, s, "final_conv_kernel", layer, 2.0 * px * d.cs * d.in_c * 9, px * (4.0 * d.in_c + (logits ? 4.0 * d.cs : 0) + (mask ? 1 : 0)));
+            Launch lp(c, s, layer, 2.0 * px * d.cs * d.in_c * 9, px * (4.0 * d.in_c + (logits ? 4.0 * d.cs : 0) + (mask ? 1 : 0)));
             HIP_TRY(launch_final_conv(i > s0 ? c->prev[i - 1] : nullptr, i > s0 ? d.F : 0, c->cvt[i], d.F, d.f_w, d.f_b, logits, mask, n, R, R, d.cs, c->bf16, s));
         }
     }
@@ -1266,7 +1282,7 @@ int gsa_decoder_forward(gsa_ctx* c, void* stream, int32_t n, const float* const*
     for (int i = c->d_s0; i < c->d_n; ++i) {   // entries below start_res are not read (they may be null)
         if (!feats[i]) return fail(c, GSA_ERR_INVALID, "feature %d is null", i);
         const int R = 4 << i;
-        Launch lp(c, s, "import_nhwc_kernel", "d.import", 0.0, 8.0 * n * R * R * c->dl[i].I);
+        Launch lp(c, s, "d.import", 0.0, 8.0 * n * R * R * c->dl[i].I);
         HIP_TRY(launch_import_nhwc(feats[i], c->din[i], n, R, R, c->dl[i].I, c->bf16, s));
         fsrc[i] = c->din[i];
     }
@@ -1389,6 +1405,17 @@ int gsa_profile_collect(gsa_ctx* c) {
     c->prof_events.clear();
     HIP_TRY(hipDeviceSynchronize());
     if (int rc = read_device_status(c)) return rc;
+    for (ProfEntry& e : c->prof_entries) {
+        if (!e.name.empty()) continue;
+        auto it = c->kernel_names.find(e.kern);
+        if (it == c->kernel_names.end()) it = c->kernel_names.emplace(e.kern, kernel_name(e.kern)).first;
+        e.name = e.layer.empty() ? it->second : it->second + " | " + e.layer;
+    }
+    if (c->prof_multi) {
+        const int k = c->prof_multi;
+        c->prof_multi = 0;
+        return fail(c, GSA_ERR_STATE, "profiling: %d launch scope(s) launched more than one kernel", k);
+    }
     return (int)c->prof_entries.size();
 }
 

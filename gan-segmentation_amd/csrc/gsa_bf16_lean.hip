@@ -16,7 +16,6 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
 namespace gsa {
@@ -352,29 +351,11 @@ __global__ __launch_bounds__(256, (EPI == EPI_SYNTH || NT == 4 || (RES && NT == 
     TFLUSH(12, (unsigned long long)items); TFLUSH(15, 1ull);
 }
 
-constexpr int kMaxDevB = 64;
-struct BState { bool attr_done = false; int cus = 0; };
-static std::mutex g_bmu;
-
 template <int EPI, bool AFF, bool RES, int NT>
 hipError_t launch_bf16_t(const ConvParams& p, int n, hipStream_t s) {
-    static BState st[kMaxDevB];
-    auto kern = conv3x3_bf16_lean<EPI, AFF, RES, NT>;
     const int nblk = p.C0 / 16;
     const size_t lds = sizeof(float) * (2 * BIMG + 2 * NT * BSEG + 64 * NT + nblk * 32);
-    if (p.device < 0 || p.device >= kMaxDevB) return hipErrorInvalidDevice;
-    int cus;
-    {
-        std::lock_guard<std::mutex> lk(g_bmu);
-        BState& d = st[p.device];
-        if (!d.attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            if (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, p.device) != hipSuccess) d.cus = 256;
-            d.attr_done = true;
-        }
-        cus = d.cus;
-    }
+    const int cus = device_cus(p.device);
     ConvParams q = p;
     q.tiles_x = p.W / 16;
     q.tiles_y = p.H / 16;
@@ -389,8 +370,7 @@ hipError_t launch_bf16_t(const ConvParams& p, int n, hipStream_t s) {
     const int per_cu = std::min((EPI == EPI_SYNTH || NT == 4 || (RES && NT == 2)) ? 2 : 3, (int)(160 * 1024 / lds));
     const int slots = std::max(1, cus * std::max(per_cu, 1) / q.groups);
     const int gx = std::min(q.total_tiles, slots);
-    hipLaunchKernelGGL(kern, dim3(gx, q.groups), dim3(256), lds, s, q);
-    return hipGetLastError();
+    return launch<conv3x3_bf16_lean<EPI, AFF, RES, NT>>(p.device, dim3(gx, q.groups), dim3(256), lds, s, q);
 }
 
 }  // namespace lean
@@ -417,13 +397,6 @@ static int bf16_lean_nt(const ConvParams& p, int n) {
     for (int nt = 4; nt > 1; nt >>= 1)
         if (groups % nt == 0 && tile_groups / nt >= 512) return nt;
     return 1;
-}
-
-const char* bf16_lean_name(const ConvParams& p, int epi, int n) {
-    static thread_local char buf[128];
-    snprintf(buf, sizeof buf, "void gsa::lean::conv3x3_bf16_lean<%d, %s, %s, %d>(gsa::ConvParams)", epi, p.aff0 ? "true" : "false", p.resid ? "true" : "false",
-             bf16_lean_nt(p, n));
-    return buf;
 }
 
 template <int NT>

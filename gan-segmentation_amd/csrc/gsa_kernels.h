@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <string>
+
 namespace gsa {
 
 // Per-(sample, channel) AdaIN coefficients: out = fmaf(x, A, B), B = fmaf(-mean, A, beta*(ys+1)+yb)
@@ -22,7 +25,7 @@ constexpr double kStatScale1 = 268435456.0;  // 2^28: quad sums
 enum Epilogue { EPI_RAW = 0, EPI_SYNTH = 1, EPI_DEC = 2 };
 
 struct ConvParams {
-    int device;      // HIP device of the launching context (per-device launch state in the launchers)
+    int device;      // HIP device of the launching context (the launch helper keeps its state per device)
     // input: up to two NHWC sources concatenated on channels (C0 then C1), both multiples of 16
     const float* src0; const Aff* aff0; int C0;   // aff0 may be null (identity)
     const float* src1; int C1;                    // src1 may be null
@@ -93,17 +96,14 @@ bool conv_uses_wino(const ConvParams& p, int epi, bool shortcut);   // true: Win
 // gsa_wino_lean.hip (round 5): the Winograd layers with one 16-channel input block and one 16-channel output group in a leaner
 // instruction stream -- speed only, the same arithmetic and bits as conv3x3_wino (GSA_WINO_LEAN=0 keeps conv3x3_wino)
 bool wino_lean_applies(const ConvParams& p, int epi);
-const char* wino_lean_name(const ConvParams& p, int epi, int n);
 hipError_t launch_wino_lean(const ConvParams& p, int epi, int n, hipStream_t s);
 bool wino_lean_fuses_torgb(const ConvParams& p, int epi, int nc);      // the lean kernel's own conditions
 bool conv_fuses_torgb(const ConvParams& p, int epi, bool shortcut, int nc);      // true: launch_conv3x3 on p (rgb_* set) also produces toRGB's uint8 image
 // gsa_bf16_lean.hip (round 5): the bf16 mode's 3x3 convolutions from 32 px on in the lean form (GSA_BF16_LEAN=0: conv3x3_mfma<..., true>)
 bool bf16_lean_applies(const ConvParams& p, int epi, bool shortcut);
-const char* bf16_lean_name(const ConvParams& p, int epi, int n);
 hipError_t launch_bf16_lean(const ConvParams& p, int epi, int n, hipStream_t s);
 // gsa_sub_lean.hip (round 5): subpixel_res<..., WINO> (fp32) in a leaner instruction stream -- speed only, same bits (GSA_SUB_LEAN=0: subpixel_res)
 bool subpixel_lean_applies(const ConvParams& p, int nt, int epi, bool sc, int kb, bool wst);
-const char* subpixel_lean_name(const ConvParams& p, int nt, int epi, bool sc, int kb, bool wst);
 hipError_t launch_subpixel_lean(const ConvParams& q, int nt, int epi, bool sc, int kb, bool wst, dim3 grid, hipStream_t s);
 hipError_t launch_subpixel(const ConvParams& p, int epi, bool shortcut, int n, hipStream_t s);   // deconv4x4s2 / sub-pixel up+conv
 bool subpixel_uses_wino(const ConvParams& p);                      // true: Winograd F(2x2,2x2) form (static rule: fp32 mode): 9 products per 2x2 class outputs instead of 163x3
@@ -141,13 +141,50 @@ hipError_t launch_final_conv(const float* src0, int C0, const float* src1, int C
 int conv_stat_rows(int H, int W, int Cout, int n);   // statistic partial rows per sample written by conv3x3 EPI_SYNTH
 int post_prow(int H, int W, int C);                  // ... written by the post kernel (upper bound: the one-row form)
 int post_rows_used(const PostParams& p);             // ... by the form launch_post picks for p
-const char* subpixel_kernel_name(const ConvParams& p, int epi, bool sc, int n);
 hipError_t launch_fill_normal(float* out, int per_sample, int n, unsigned long long first_index, unsigned plane,
                               unsigned long long seed, hipStream_t s);
 hipError_t launch_seg_eval(const float* logits, const int8_t* labels, int n, int classes, int H, int W,
                            unsigned long long* confusion, unsigned long long* loss_fixed, hipStream_t s);
-const char* conv3x3_kernel_name(const ConvParams& p, int epi, bool sc, int n);
-const char* conv_geom_name(int H, int W, int Cout, int n);   // "tile16,cout64" -- for profile labels
-const char* subpixel_geom_name(int H, int W, int Cout, int n);
+
+// ---- launch helper of the generate path (gsa_kernels.hip, gsa_*_lean.hip) --------------------------------------------------
+// The first use of a kernel on a device allows it the whole 160 KB of LDS (less its static LDS); the CU count and the occupancy
+// answers are kept per device.  A process may hold contexts on several GPUs (ImageGenerator(gpu_ids=[0, 1, ...]), reference
+// image_generator.py:17): one mutex makes the first-use path safe for the "one context per (device, host thread)" contract of
+// include/gsa.h.  A device outside [0, kMaxDevices) is hipErrorInvalidDevice.  After the first use a launch takes no lock.
+constexpr int kMaxDevices = 64;
+int device_cus(int device);       // CU count (256 when the runtime cannot say)
+int current_device();             // the calling thread's device, for the launchers whose parameters carry none (-1: unknown)
+hipError_t allow_max_lds(const void* kern);
+hipError_t cached_occupancy(const void* kern, int device, int block, size_t lds, int* wgs_per_cu);
+void note_launch(const void* kern);
+// what the calling thread launched through launch() since the last call (the profiler's label): the last kernel and the count
+struct LaunchRecord { const void* kern = nullptr; int count = 0; };
+LaunchRecord take_launch_record();
+std::string kernel_name(const void* kern);     // the demangled C++ signature, as rocprofv3 prints it
+
+template <auto K>
+hipError_t prepare_kernel(int device) {
+    static std::atomic<uint64_t> ready{0};     // one bit per device
+    if (device < 0 || device >= kMaxDevices) return hipErrorInvalidDevice;
+    if (ready.load(std::memory_order_acquire) >> device & 1) return hipSuccess;
+    if (hipError_t e = allow_max_lds(reinterpret_cast<const void*>(K))) return e;
+    ready.fetch_or(1ull << device, std::memory_order_release);
+    return hipSuccess;
+}
+
+// resident workgroups per CU of K with `block` threads and `lds` bytes of dynamic LDS, clamped to 1..8 (cached)
+template <auto K>
+hipError_t kernel_occupancy(int device, int block, size_t lds, int* wgs_per_cu) {
+    if (hipError_t e = prepare_kernel<K>(device)) return e;
+    return cached_occupancy(reinterpret_cast<const void*>(K), device, block, lds, wgs_per_cu);
+}
+
+template <auto K, class... Args>
+hipError_t launch(int device, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+    if (hipError_t e = prepare_kernel<K>(device)) return e;
+    hipLaunchKernelGGL(K, grid, block, lds, s, args...);
+    note_launch(reinterpret_cast<const void*>(K));
+    return hipGetLastError();
+}
 
 }  // namespace gsa

@@ -23,9 +23,13 @@
 #include "gsa_kernels.h"
 #include "gsa_dev.h"
 
+#include <cxxabi.h>
+
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
+#include <vector>
 
 // wave priority during the MFMA phase of conv3x3_mfma (the wave multiplying wins the SIMD's issue slot over the wave
 // staging): +0.5-1 % on the step in A/B runs; the same in the stride-2 kernels measured -0.5 % and is not used
@@ -3740,27 +3744,71 @@ __global__ __launch_bounds__(256) void fill_normal_kernel(float* out, int per_sa
 // ========================================================================================
 // host-side launchers
 
-// ---- per-device launch state -------------------------------------------------------------
-// hipFuncSetAttribute, the CU count and the occupancy answers belong to ONE device: a process may hold contexts
-// on several GPUs (ImageGenerator(gpu_ids=[0, 1, ...]), reference image_generator.py:17), so every launcher keeps
-// one LaunchState per (kernel instantiation, device), and a mutex makes the first-use path safe for the "one
-// context per (device, host thread)" contract of include/gsa.h.
-constexpr int kMaxDevices = 64;
-struct LaunchState {
-    bool attr_done = false;
-    size_t occ_lds[8] = {0};
-    int occ_k[8] = {0}, occ_n = 0;
-};
-static std::mutex g_launch_mu;
+// ---- launch helper (gsa_kernels.h) -----------------------------------------------------------------------------------------
+namespace {
+struct Occupancy { const void* kern; int device; size_t lds; int wgs_per_cu; };
+std::mutex g_launch_mu;
+std::vector<Occupancy> g_occupancy;     // a few footprints per kernel
+std::atomic<int> g_cus[kMaxDevices];
+thread_local LaunchRecord t_record;
+}  // namespace
 
-static int device_cus(int dev) {     // caller holds g_launch_mu
-    static int cus[kMaxDevices] = {0};
-    if (dev < 0 || dev >= kMaxDevices) return 256;
-    if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus[dev] = 256;
-    return cus[dev];
+int device_cus(int device) {
+    if (device < 0 || device >= kMaxDevices) return 256;
+    int cus = g_cus[device].load(std::memory_order_relaxed);
+    if (!cus) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 256;
+        g_cus[device].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
 }
 
-// first launch of `kern` on device `dev`: allow the full 160 KB of dynamic LDS
+int current_device() {
+    int device = -1;
+    return hipGetDevice(&device) == hipSuccess ? device : -1;
+}
+
+hipError_t allow_max_lds(const void* kern) {
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    hipFuncAttributes fa{};
+    hipError_t e = hipFuncGetAttributes(&fa, kern);
+    if (e == hipSuccess) e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)fa.sharedSizeBytes);
+    return e;
+}
+
+hipError_t cached_occupancy(const void* kern, int device, int block, size_t lds, int* wgs_per_cu) {
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    for (const Occupancy& o : g_occupancy)
+        if (o.kern == kern && o.device == device && o.lds == lds) { *wgs_per_cu = o.wgs_per_cu; return hipSuccess; }
+    int k = 0;
+    if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, kern, block, lds)) return e;
+    *wgs_per_cu = k < 1 ? 1 : (k > 8 ? 8 : k);
+    g_occupancy.push_back({kern, device, lds, *wgs_per_cu});
+    if (getenv("GSA_VERBOSE")) fprintf(stderr, "gsa: %s lds %zu B -> %d workgroups/CU\n", kernel_name(kern).c_str(), lds, k);
+    return hipSuccess;
+}
+
+void note_launch(const void* kern) {
+    t_record.kern = kern;
+    ++t_record.count;
+}
+
+LaunchRecord take_launch_record() {
+    const LaunchRecord r = t_record;
+    t_record = LaunchRecord{};
+    return r;
+}
+
+std::string kernel_name(const void* kern) {
+    const char* raw = hipKernelNameRefByPtr(kern, nullptr);
+    if (!raw) return "?";
+    int status = -1;
+    char* dem = strncmp(raw, "_Z", 2) == 0 ? abi::__cxa_demangle(raw, nullptr, nullptr, &status) : nullptr;
+    std::string name = dem && status == 0 ? dem : raw;
+    free(dem);
+    return name;
+}
+
 // few statistic rows (GSA_FEWROWS=0: one row per workgroup / wave as in round 1): producers with more workgroups than
 // kDirectRows ADD to row (workgroup mod kDirectRows) of the all-zero `partials` instead of writing a row each, so that
 // finalize_kernel always finds at most kDirectRows rows per sample: one block per channel group, every row load in flight at
@@ -3768,14 +3816,6 @@ static int device_cus(int dev) {     // caller holds g_launch_mu
 static bool few_rows() {
     static const bool enabled = !(getenv("GSA_FEWROWS") && atoi(getenv("GSA_FEWROWS")) == 0);
     return enabled;
-}
-
-template <class K>
-static hipError_t prepare_kernel(K kern, LaunchState& st) {
-    if (st.attr_done) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) st.attr_done = true;
-    return e;
 }
 
 // ---- conv3x3 geometry selection --------------------------------------------------------
@@ -3809,15 +3849,6 @@ int conv_stat_rows(int H, int W, int Cout, int n) {   // rows of the non-special
 
 int post_prow(int H, int W, int C) { return (H * (W / 4) * (C / 4) + 255) / 256; }
 
-// template arguments of the instantiation the launcher picks: "16, 16, 4, 1, 1" -- profile labels
-// spell the kernel exactly as rocprofv3 prints it
-const char* conv_geom_name(int H, int W, int Cout, int n) {
-    static thread_local char buf[48];
-    const ConvGeom c = pick_geom(H, W, Cout, n);
-    snprintf(buf, sizeof buf, "%d, %d, %d, %d, %d", c.th, c.th, c.wm, c.wn, c.nt);
-    return buf;
-}
-
 template <int TH, int TW, int WM, int WN, int NT, int EPI, bool SC, bool BF>
 static hipError_t launch_conv_t(const ConvParams& p, int n, hipStream_t s) {
     constexpr int Q = NT * WN, COUT_T = 16 * Q;
@@ -3832,30 +3863,10 @@ static hipError_t launch_conv_t(const ConvParams& p, int n, hipStream_t s) {
     const int wslots = wres ? nblk_all * Q * 9 * TS : NBUF * Q * 9 * TS;
     const size_t lds = sizeof(float) * (NBUF * (TH + 2) * RS + wslots + (SC ? Q * TS : 0)) +
                        (p.aff0 ? sizeof(float4) * (NBUF == 2 ? 32 : p.C0) : 0);   // double-buffered form: 2 x 16 AdaIN entries
-    auto kern = conv3x3_mfma<TH, TW, WM, WN, NT, EPI, SC, BF>;
-    if (p.device < 0 || p.device >= kMaxDevices) return hipErrorInvalidDevice;
-    static LaunchState states[kMaxDevices];
-    int num_cus = 0, wgs_per_cu = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        LaunchState& st = states[p.device];
-        hipError_t e = prepare_kernel(kern, st);
-        if (e != hipSuccess) return e;
-        num_cus = device_cus(p.device);
-        // resident workgroups per CU for this LDS footprint (a few distinct footprints per instantiation: cached)
-        for (int i = 0; i < st.occ_n; ++i)
-            if (st.occ_lds[i] == lds) wgs_per_cu = st.occ_k[i];
-        if (!wgs_per_cu) {
-            int k = 0;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, reinterpret_cast<const void*>(kern), 64 * WM * WN, lds);
-            if (e != hipSuccess) return e;
-            wgs_per_cu = k < 1 ? 1 : (k > 8 ? 8 : k);
-            if (st.occ_n < 8) { st.occ_lds[st.occ_n] = lds; st.occ_k[st.occ_n] = wgs_per_cu; ++st.occ_n; }
-            if (getenv("GSA_VERBOSE"))
-                fprintf(stderr, "gsa: conv3x3_mfma<%d,%d,%d,%d,%d,%d,%d,%d> lds %zu B%s -> %d workgroups/CU\n", TH, TW, WM, WN, NT, EPI, (int)SC,
-                        (int)BF, lds, wres ? " (resident weights)" : "", k);
-        }
-    }
+    constexpr auto kern = conv3x3_mfma<TH, TW, WM, WN, NT, EPI, SC, BF>;
+    int wgs_per_cu = 0;
+    if (hipError_t e = kernel_occupancy<kern>(p.device, 64 * WM * WN, lds, &wgs_per_cu)) return e;
+    const int num_cus = device_cus(p.device);
     ConvParams q = p;
     q.w_resident = wres ? 1 : 0;
     q.tiles_x = p.W / TW;
@@ -3871,8 +3882,7 @@ static hipError_t launch_conv_t(const ConvParams& p, int n, hipStream_t s) {
     q.stats_direct = (direct_enabled && EPI == EPI_SYNTH && NBUF == 2 && persistent && p.partials != nullptr) ? 1 : 0;
     if (q.stats_direct) q.prow = kDirectRows;      // the rows are all zero between layers (finalize_kernel clears what it read)
     if (p.stat_rows_host) *p.stat_rows_host = q.prow;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WM * WN), lds, s, q);
-    return hipGetLastError();
+    return launch<kern>(p.device, dim3(grid), dim3(64 * WM * WN), lds, s, q);
 }
 
 template <int TH, int TW, int WM, int WN, int NT, bool BF>
@@ -3906,14 +3916,6 @@ static hipError_t launch_ksplit_t(const ConvParams& p, int n, hipStream_t s) {
     constexpr int MT = (TH / 4) * (TH / 4), PX = BF ? 8 : 16, TS = BF ? 128 : 256;
     constexpr int RS = (TH + 2) * PX + (BF ? 4 : 8), IMG = (TH + 2) * RS, SEG = 9 * TS;
     const size_t lds = sizeof(float) * (2 * 4 * IMG + 2 * 4 * SEG) + sizeof(float4) * (2 * 4 * 16 + 4 * MT * 64) + 2 * 16 * sizeof(unsigned long long) + 16;
-    auto kern = conv3x3_ksplit<TH, EPI, BF, PS>;
-    if (p.device < 0 || p.device >= kMaxDevices) return hipErrorInvalidDevice;
-    static LaunchState states[kMaxDevices];
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        hipError_t e = prepare_kernel(kern, states[p.device]);
-        if (e != hipSuccess) return e;
-    }
     ConvParams q = p;
     q.tiles_x = p.W / TH;
     q.tiles_y = p.H / TH;
@@ -3921,8 +3923,7 @@ static hipError_t launch_ksplit_t(const ConvParams& p, int n, hipStream_t s) {
     q.prow = q.tiles_x * q.tiles_y * MT;
     q.stats_direct = 0;
     if (p.stat_rows_host) *p.stat_rows_host = q.prow;
-    hipLaunchKernelGGL(kern, dim3(q.tiles_x * q.tiles_y, q.groups, n), dim3(256 * PS), lds, s, q);
-    return hipGetLastError();
+    return launch<conv3x3_ksplit<TH, EPI, BF, PS>>(p.device, dim3(q.tiles_x * q.tiles_y, q.groups, n), dim3(256 * PS), lds, s, q);
 }
 
 // waves per workgroup of the 8x8 form: 8 (patch split) unless GSA_KSPLIT_PS=1 (speed only, same bits)
@@ -3966,28 +3967,11 @@ static hipError_t launch_wino_t(const ConvParams& p, int n, hipStream_t s) {
     const int nblk = p.C0 / 16;
     const bool wres = (size_t)nblk * NT * SEG * sizeof(float) <= (NT == 1 ? 36 : 72) * 1024;      // whole panel of the group resident (<= 32 input channels)
     const size_t lds = sizeof(float) * (2 * 18 * RS + (wres ? nblk : 2) * GW * NT * SEG) + (CHUNK ? 0 : 32 * sizeof(float4));
-    auto kern = conv3x3_wino<EPI, NT, CHUNK, AFF, GW, TW>;
+    constexpr auto kern = conv3x3_wino<EPI, NT, CHUNK, AFF, GW, TW>;
     if (TW == 2 && !wres) return hipErrorInvalidValue;      // two tiles per workgroup: resident weight panel only
-    if (p.device < 0 || p.device >= kMaxDevices) return hipErrorInvalidDevice;
-    static LaunchState states[kMaxDevices];
-    int num_cus = 0, wgs_per_cu = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        LaunchState& st = states[p.device];
-        hipError_t e = prepare_kernel(kern, st);
-        if (e != hipSuccess) return e;
-        num_cus = device_cus(p.device);
-        for (int i = 0; i < st.occ_n; ++i)
-            if (st.occ_lds[i] == lds) wgs_per_cu = st.occ_k[i];
-        if (!wgs_per_cu) {
-            int k = 0;
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&k, reinterpret_cast<const void*>(kern), 256 * GW * TW, lds);
-            if (e != hipSuccess) return e;
-            wgs_per_cu = k < 1 ? 1 : (k > 8 ? 8 : k);
-            if (st.occ_n < 8) { st.occ_lds[st.occ_n] = lds; st.occ_k[st.occ_n] = wgs_per_cu; ++st.occ_n; }
-            if (getenv("GSA_VERBOSE")) fprintf(stderr, "gsa: conv3x3_wino<%d,%d,%d,%d,%d> lds %zu B%s -> %d workgroups/CU\n", EPI, NT, (int)CHUNK, (int)AFF, GW, lds, wres ? " (resident weights)" : "", k);
-        }
-    }
+    int wgs_per_cu = 0;
+    if (hipError_t e = kernel_occupancy<kern>(p.device, 256 * GW * TW, lds, &wgs_per_cu)) return e;
+    const int num_cus = device_cus(p.device);
     ConvParams q = p;
     q.wpk = p.wino;
     q.w_resident = wres ? 1 : 0;
@@ -4016,9 +4000,8 @@ static hipError_t launch_wino_t(const ConvParams& p, int n, hipStream_t s) {
     static const bool gm_enabled = !(getenv("GSA_WINO_GM") && atoi(getenv("GSA_WINO_GM")) == 0);
     q.group_minor = (gm_enabled && !persistent && q.groups > 1 && q.total_tiles % 8 == 0 &&
                      (size_t)16 * p.C0 * p.Cout * sizeof(float) <= (size_t)2 << 20) ? 1 : 0;
-    if (q.group_minor) hipLaunchKernelGGL(kern, dim3(q.total_tiles * q.groups), dim3(256 * GW * TW), lds, s, q);
-    else hipLaunchKernelGGL(kern, dim3(gx, q.groups), dim3(256 * GW * TW), lds, s, q);
-    return hipGetLastError();
+    const dim3 grid = q.group_minor ? dim3(q.total_tiles * q.groups) : dim3(gx, q.groups);
+    return launch<kern>(p.device, grid, dim3(256 * GW * TW), lds, s, q);
 }
 
 // ---- Winograd F(4x4,3x3) form (round 4).  Static rule (oracle/c/gsa_oracle.c use_wino43): a layer without a residual epilogue
@@ -4040,16 +4023,7 @@ static hipError_t launch_wino43_t(const ConvParams& p, int n, hipStream_t s) {
     constexpr int IMG = 12 * 64 * 4, SEG = 36 * 128;      // conv3x3_wino43: image buffer of a wave, weight panel of an item (8-channel blocks)
     const size_t lds = sizeof(float) * (4 * 2 * IMG + 2 * SEG);
     if (!p.zeros) return hipErrorInvalidValue;
-    auto kern = conv3x3_wino43<EPI>;
-    if (p.device < 0 || p.device >= kMaxDevices) return hipErrorInvalidDevice;
-    static LaunchState states[kMaxDevices];
-    int num_cus = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        hipError_t e = prepare_kernel(kern, states[p.device]);
-        if (e != hipSuccess) return e;
-        num_cus = device_cus(p.device);
-    }
+    const int num_cus = device_cus(p.device);
     ConvParams q = p;
     q.wpk = p.wino;
     q.tiles_x = p.W / 16;
@@ -4064,8 +4038,7 @@ static hipError_t launch_wino43_t(const ConvParams& p, int n, hipStream_t s) {
     q.stats_direct = 1;
     q.prow = kDirectRows;      // the sums go straight to kDirectRows zeroed rows per sample (finalize_kernel clears what it read)
     if (p.stat_rows_host) *p.stat_rows_host = q.prow;
-    hipLaunchKernelGGL(kern, dim3(gx, q.groups), dim3(256), lds, s, q);
-    return hipGetLastError();
+    return launch<conv3x3_wino43<EPI>>(p.device, dim3(gx, q.groups), dim3(256), lds, s, q);
 }
 
 static hipError_t launch_wino43(const ConvParams& p, int epi, int n, hipStream_t s) {
@@ -4108,16 +4081,7 @@ template <int EPI, bool AFF>
 static hipError_t launch_wino_dma_t(const ConvParams& p, int n, hipStream_t s) {
     constexpr int IMGF = 21 * 256, SEG = 16 * 256;
     const size_t lds = sizeof(float) * (2 * IMGF + 2 * SEG);
-    auto kern = conv3x3_wino_dma<EPI, AFF>;
-    if (p.device < 0 || p.device >= kMaxDevices) return hipErrorInvalidDevice;
-    static LaunchState states[kMaxDevices];
-    int num_cus = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        hipError_t e = prepare_kernel(kern, states[p.device]);
-        if (e != hipSuccess) return e;
-        num_cus = device_cus(p.device);
-    }
+    const int num_cus = device_cus(p.device);
     ConvParams q = p;
     q.wpk = p.wino;
     q.tiles_x = p.W / 16;
@@ -4130,8 +4094,7 @@ static hipError_t launch_wino_dma_t(const ConvParams& p, int n, hipStream_t s) {
     q.stats_direct = 1;
     q.prow = kDirectRows;
     if (p.stat_rows_host) *p.stat_rows_host = q.prow;
-    hipLaunchKernelGGL(kern, dim3(gx, q.groups), dim3(256), lds, s, q);
-    return hipGetLastError();
+    return launch<conv3x3_wino_dma<EPI, AFF>>(p.device, dim3(gx, q.groups), dim3(256), lds, s, q);
 }
 
 static hipError_t launch_wino_dma(const ConvParams& p, int epi, int n, hipStream_t s) {
@@ -4151,15 +4114,28 @@ static bool wino_dma(const ConvParams&, int) { return false; }
 static int wino_tw(const ConvParams&) { return 1; }
 #endif
 
-static hipError_t launch_wino(const ConvParams& p, int epi, int n, hipStream_t s) {
-#if GSA_EXPERIMENTS      // an explicitly selected experiment wins over the lean kernels
-    if (wino_dma(p, epi) && wino_nt(p) == 1) return launch_wino_dma(p, epi, n, s);
-    if (wino_tw(p) == 2) {
-        if (epi == EPI_SYNTH) return p.aff0 ? launch_wino_t<EPI_SYNTH, 1, false, true, 1, 2>(p, n, s) : launch_wino_t<EPI_SYNTH, 1, false, false, 1, 2>(p, n, s);
-        return p.aff0 ? launch_wino_t<EPI_DEC, 1, false, true, 1, 2>(p, n, s) : launch_wino_t<EPI_DEC, 1, false, false, 1, 2>(p, n, s);
-    }
+// The kernel a Winograd layer (conv_uses_wino) runs.  An explicitly selected experiment wins over the lean kernels.
+enum class WinoForm { F43, Dma, TwoTiles, Lean, General };
+static WinoForm wino_form(const ConvParams& p, int epi, bool sc) {
+    if (conv_uses_wino43(p, epi, sc)) return WinoForm::F43;
+    if (wino_dma(p, epi) && wino_nt(p) == 1) return WinoForm::Dma;
+    if (wino_tw(p) == 2) return WinoForm::TwoTiles;
+    if (wino_lean_applies(p, epi)) return WinoForm::Lean;
+    return WinoForm::General;
+}
+
+static hipError_t launch_wino(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
+    switch (wino_form(p, epi, sc)) {
+#if GSA_EXPERIMENTS
+        case WinoForm::F43: return launch_wino43(p, epi, n, s);
+        case WinoForm::Dma: return launch_wino_dma(p, epi, n, s);
+        case WinoForm::TwoTiles:
+            if (epi == EPI_SYNTH) return p.aff0 ? launch_wino_t<EPI_SYNTH, 1, false, true, 1, 2>(p, n, s) : launch_wino_t<EPI_SYNTH, 1, false, false, 1, 2>(p, n, s);
+            return p.aff0 ? launch_wino_t<EPI_DEC, 1, false, true, 1, 2>(p, n, s) : launch_wino_t<EPI_DEC, 1, false, false, 1, 2>(p, n, s);
 #endif
-    if (wino_lean_applies(p, epi)) return launch_wino_lean(p, epi, n, s);
+        case WinoForm::Lean: return launch_wino_lean(p, epi, n, s);
+        default: break;
+    }
     const int nt = wino_nt(p);
     const int gw = wino_gw(p);
     const bool ch = wino_chunk(p);
@@ -4179,48 +4155,12 @@ static hipError_t launch_wino(const ConvParams& p, int epi, int n, hipStream_t s
 // true: launch_conv3x3(p, epi, sc) with p.rgb_* set also writes toRGB's uint8 image -- i.e. the call reaches the lean 16 -> 16 kernel (an
 // experiment switch that takes the layer elsewhere, or the F(4x4,3x3) form, rules it out: they know nothing of rgb_img)
 bool conv_fuses_torgb(const ConvParams& p, int epi, bool sc, int nc) {
-    if (!conv_uses_wino(p, epi, sc) || conv_uses_wino43(p, epi, sc)) return false;
-    if ((wino_dma(p, epi) && wino_nt(p) == 1) || wino_tw(p) == 2) return false;
-    return wino_lean_fuses_torgb(p, epi, nc);
-}
-
-// exact C++ name of the instantiation launch_conv3x3 picks (profile labels spell kernels as rocprofv3 prints them)
-const char* conv3x3_kernel_name(const ConvParams& p, int epi, bool sc, int n) {
-    static thread_local char buf[128];
-    if (conv_uses_wino43(p, epi, sc)) {
-        snprintf(buf, sizeof buf, "void gsa::conv3x3_wino43<%d>(gsa::ConvParams)", epi);
-        return buf;
-    }
-    if (conv_uses_wino(p, epi, sc) && !(wino_dma(p, epi) && wino_nt(p) == 1) && wino_tw(p) != 2 && wino_lean_applies(p, epi)) return wino_lean_name(p, epi, n);
-    if (conv_uses_wino(p, epi, sc) && wino_dma(p, epi) && wino_nt(p) == 1) {
-        snprintf(buf, sizeof buf, "void gsa::conv3x3_wino_dma<%d, %s>(gsa::ConvParams)", epi, p.aff0 ? "true" : "false");
-        return buf;
-    }
-    if (conv_uses_wino(p, epi, sc) && wino_tw(p) == 2) {
-        snprintf(buf, sizeof buf, "void gsa::conv3x3_wino<%d, 1, false, %s, 1, 2>(gsa::ConvParams)", epi, p.aff0 ? "true" : "false");
-        return buf;
-    }
-    if (conv_uses_wino(p, epi, sc)) {
-        snprintf(buf, sizeof buf, "void gsa::conv3x3_wino<%d, %d, %s, %s, %d>(gsa::ConvParams)", epi, wino_nt(p), wino_chunk(p) ? "true" : "false", p.aff0 ? "true" : "false", wino_gw(p));
-        return buf;
-    }
-    if (conv_uses_ksplit(p, sc)) {
-        snprintf(buf, sizeof buf, "void gsa::conv3x3_ksplit<%d, %d, %s, %d>(gsa::ConvParams)", p.H == 4 ? 4 : 8, epi, p.bf16 ? "true" : "false", p.H == 4 ? 1 : ksplit_ps());
-        return buf;
-    }
-    if (bf16_lean_applies(p, epi, sc)) return bf16_lean_name(p, epi, n);
-    const ConvGeom c = pick_geom(p.H, p.W, p.Cout, n);
-    snprintf(buf, sizeof buf, "void gsa::conv3x3_mfma<%d, %d, %d, %d, %d, %d, %s, %s>(gsa::ConvParams)", c.th, c.th, c.wm, c.wn, c.nt,
-             epi, sc ? "true" : "false", p.bf16 ? "true" : "false");
-    return buf;
+    return conv_uses_wino(p, epi, sc) && wino_form(p, epi, sc) == WinoForm::Lean && wino_lean_fuses_torgb(p, epi, nc);
 }
 
 hipError_t launch_conv3x3(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
     if (p.H != p.W || (p.H & (p.H - 1)) || p.H < 4 || p.Cout % 16 || p.C0 % 16 || p.C1 % 16) return hipErrorInvalidValue;
-#if GSA_EXPERIMENTS
-    if (conv_uses_wino43(p, epi, sc)) return launch_wino43(p, epi, n, s);
-#endif
-    if (conv_uses_wino(p, epi, sc)) return launch_wino(p, epi, n, s);
+    if (conv_uses_wino(p, epi, sc)) return launch_wino(p, epi, sc, n, s);
     if (conv_uses_ksplit(p, sc)) return launch_ksplit(p, epi, n, s);
     if (bf16_lean_applies(p, epi, sc)) return launch_bf16_lean(p, epi, n, s);
     const ConvGeom c = pick_geom(p.H, p.W, p.Cout, n);
@@ -4246,19 +4186,10 @@ template <int NT, int EPI, bool SC, bool BF, bool WINO = false>
 static hipError_t launch_subpixel_t(const ConvParams& p, int n, hipStream_t s) {
     constexpr int COUT_T = 16 * NT, TS = BF ? 128 : 256;
     const size_t lds = sizeof(float) * (10 * (10 * (BF ? 8 : 16) + (BF || WINO ? 4 : 8)) + NT * 16 * TS + (SC ? NT * TS : 0)) + (p.aff0 ? sizeof(float4) * p.C0 : 0);
-    auto kern = subpixel_mfma<NT, EPI, SC, BF, WINO>;
-    if (p.device < 0 || p.device >= kMaxDevices) return hipErrorInvalidDevice;
-    static LaunchState states[kMaxDevices];
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        hipError_t e = prepare_kernel(kern, states[p.device]);
-        if (e != hipSuccess) return e;
-    }
     ConvParams q = p;
     q.tiles_x = p.W / 16;
-    dim3 grid((p.H / 16) * (p.W / 16), p.Cout / COUT_T, n);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, q);
-    return hipGetLastError();
+    const dim3 grid((p.H / 16) * (p.W / 16), p.Cout / COUT_T, n);
+    return launch<subpixel_mfma<NT, EPI, SC, BF, WINO>>(p.device, grid, dim3(256), lds, s, q);
 }
 
 // channel blocks per item of subpixel_res: 2 when the block count is even and the doubled activation buffers still fit
@@ -4267,16 +4198,7 @@ static int subpixel_res_kb(const ConvParams& p);
 // persistent form with the LDS-resident weight panel (subpixel_res): one 512-thread workgroup per CU
 template <int NT, int EPI, bool SC, bool BF, int KB, bool WINO>
 static hipError_t launch_subpixel_res_k(const ConvParams& p, int n, size_t lds, hipStream_t s) {
-    auto kern = subpixel_res<NT, EPI, SC, BF, KB, false, WINO>;
-    if (p.device < 0 || p.device >= kMaxDevices) return hipErrorInvalidDevice;
-    static LaunchState states[kMaxDevices];
-    int num_cus = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        hipError_t e = prepare_kernel(kern, states[p.device]);
-        if (e != hipSuccess) return e;
-        num_cus = device_cus(p.device);
-    }
+    const int num_cus = device_cus(p.device);
     ConvParams q = p;
     q.tiles_x = p.W / 16;
     q.tiles_y = p.H / 16;
@@ -4284,39 +4206,25 @@ static hipError_t launch_subpixel_res_k(const ConvParams& p, int n, size_t lds, 
     q.total_tiles = q.tiles_x * q.tiles_y * n;
     const int grid = std::min(num_cus, (q.total_tiles + 1) / 2);
     if (WINO && !BF && subpixel_lean_applies(q, NT, EPI, SC, KB, false)) return launch_subpixel_lean(q, NT, EPI, SC, KB, false, dim3(grid), s);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, q);
-    return hipGetLastError();
+    return launch<subpixel_res<NT, EPI, SC, BF, KB, false, WINO>>(p.device, dim3(grid), dim3(512), lds, s, q);
 }
 
 // streamed-weights form: grid (workgroups per channel group, channel groups)
 template <int NT, int EPI, bool SC, bool BF, bool WINO = false>
 static hipError_t launch_subpixel_wst_t(const ConvParams& p, int n, size_t lds, int wgs_per_g, hipStream_t s) {
-    auto kern = subpixel_res<NT, EPI, SC, BF, 1, true, WINO>;
-    if (p.device < 0 || p.device >= kMaxDevices) return hipErrorInvalidDevice;
-    static LaunchState states[kMaxDevices];
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        hipError_t e = prepare_kernel(kern, states[p.device]);
-        if (e != hipSuccess) return e;
-    }
     ConvParams q = p;
     q.tiles_x = p.W / 16;
     q.tiles_y = p.H / 16;
     q.groups = p.Cout / (16 * NT);
     q.total_tiles = q.tiles_x * q.tiles_y * n;       // per channel group
     if (WINO && !BF && subpixel_lean_applies(q, NT, EPI, SC, 1, true)) return launch_subpixel_lean(q, NT, EPI, SC, 1, true, dim3(wgs_per_g, q.groups), s);
-    hipLaunchKernelGGL(kern, dim3(wgs_per_g, q.groups), dim3(512), lds, s, q);
-    return hipGetLastError();
+    return launch<subpixel_res<NT, EPI, SC, BF, 1, true, WINO>>(p.device, dim3(wgs_per_g, q.groups), dim3(512), lds, s, q);
 }
 
 // Streamed form: LDS bytes and workgroups per channel group, or 0 when it does not pay (fewer than 2 tiles per half)
 static size_t subpixel_wst_lds(const ConvParams& p, int ct, bool sc, int n, int* wgs_per_g) {
     static const bool enabled = !(getenv("GSA_SUBWST") && atoi(getenv("GSA_SUBWST")) == 0);
-    int num_cus;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        num_cus = device_cus(p.device);
-    }
+    const int num_cus = device_cus(p.device);
     if (!enabled || p.Cout % ct) return 0;
     const int ts = p.bf16 ? 128 : 256, rs = sub_rs(p);
     const int nt = ct / 16, groups = p.Cout / ct;
@@ -4362,40 +4270,11 @@ static int subpixel_res_kb(const ConvParams& p) {
 }
 
 // widest channel tile that still gives the chip >= 2 workgroups per CU (else the narrowest)
-static int subpixel_cout_tile(int H, int W, int Cout, int n, bool wino = false) {
+static int subpixel_cout_tile(int H, int W, int Cout, int n, bool wino) {
     const long tiles = (long)(H / 16) * (W / 16) * n;
     for (int ct = wino ? 32 : 64; ct >= 16; ct /= 2)      // Winograd form: nine accumulator vectors per 16 channels -- at most 32 per workgroup
         if (Cout % ct == 0 && (tiles * (Cout / ct) >= 512 || ct == 16)) return ct;
     return 16;
-}
-
-// exact C++ name of the instantiation launch_subpixel picks (profile labels)
-const char* subpixel_kernel_name(const ConvParams& p, int epi, bool sc, int n) {
-    static thread_local char buf[128];
-    const char* wn = sub_wino(p) ? "true" : "false";
-    const int ct = subpixel_cout_tile(p.H, p.W, p.Cout, n, sub_wino(p));
-    const bool res = subpixel_res_lds(p, ct, sc, n) != 0;
-    int wgs_per_g = 0;
-    if (res && sub_wino(p) && !p.bf16 && subpixel_lean_applies(p, ct / 16, epi, sc, subpixel_res_kb(p), false))
-        return subpixel_lean_name(p, ct / 16, epi, sc, subpixel_res_kb(p), false);
-    if (!res && sub_wino(p) && !p.bf16 && subpixel_wst_lds(p, ct, sc, n, &wgs_per_g) && subpixel_lean_applies(p, ct / 16, epi, sc, 1, true))
-        return subpixel_lean_name(p, ct / 16, epi, sc, 1, true);
-    if (res)
-        snprintf(buf, sizeof buf, "void gsa::subpixel_res<%d, %d, %s, %s, %d, false, %s>(gsa::ConvParams)", ct / 16, epi, sc ? "true" : "false",
-                 p.bf16 ? "true" : "false", subpixel_res_kb(p), wn);
-    else if (subpixel_wst_lds(p, ct, sc, n, &wgs_per_g))
-        snprintf(buf, sizeof buf, "void gsa::subpixel_res<%d, %d, %s, %s, 1, true, %s>(gsa::ConvParams)", ct / 16, epi, sc ? "true" : "false",
-                 p.bf16 ? "true" : "false", wn);
-    else
-        snprintf(buf, sizeof buf, "void gsa::subpixel_mfma<%d, %d, %s, %s, %s>(gsa::ConvParams)", ct / 16, epi, sc ? "true" : "false",
-                 p.bf16 ? "true" : "false", wn);
-    return buf;
-}
-
-const char* subpixel_geom_name(int H, int W, int Cout, int n) {
-    static thread_local char buf[32];
-    snprintf(buf, sizeof buf, "%d", subpixel_cout_tile(H, W, Cout, n) / 16);   // NT (direct form)
-    return buf;
 }
 
 // deconv 4x4 s2 p1, or nearest-x2 + conv3x3 with host-presummed weights (same kernel)
@@ -4498,14 +4377,15 @@ hipError_t launch_post(const PostParams& p, int n, hipStream_t s) {
     // the packed-arithmetic form (gsa_post_lean.hip): four rows per thread, a wave's 64 threads inside one row group
     if (rpt == 4 && post_pk_mode() > 0 && ((p.W / 4) * (p.C / 4)) % 64 == 0)
         return launch_post_pk(q, grid, lds + sizeof(float) * 9 * p.C, s);
+    const int dev = current_device();
 #define GSA_POST(BF) \
-    if (rpt == 8) hipLaunchKernelGGL((post_rows_kernel<8, BF>), grid, dim3(256), lds, s, q); \
-    else if (rpt == 4) hipLaunchKernelGGL((post_rows_kernel<4, BF>), grid, dim3(256), lds, s, q); \
-    else if (rpt == 2) hipLaunchKernelGGL((post_rows_kernel<2, BF>), grid, dim3(256), lds, s, q); \
-    else hipLaunchKernelGGL(post_kernel<BF>, grid, dim3(256), lds, s, q);
-    if (p.bf16) { GSA_POST(true) } else { GSA_POST(false) }
+    if (rpt == 8) return launch<post_rows_kernel<8, BF>>(dev, grid, dim3(256), lds, s, q); \
+    if (rpt == 4) return launch<post_rows_kernel<4, BF>>(dev, grid, dim3(256), lds, s, q); \
+    if (rpt == 2) return launch<post_rows_kernel<2, BF>>(dev, grid, dim3(256), lds, s, q); \
+    return launch<post_kernel<BF>>(dev, grid, dim3(256), lds, s, q);
+    if (p.bf16) { GSA_POST(true) }
+    GSA_POST(false)
 #undef GSA_POST
-    return hipGetLastError();
 }
 
 // whole-plane K-split tiles (4 and 8 px) finalize in the kernel when the caller supplies the finalize operands (GSA_FUSEFIN=0: never)
@@ -4521,9 +4401,8 @@ bool post_fuses_finalize(const PostParams& p) {
 hipError_t launch_post_fin(const PostParams& p, const FinalizeParams& f, int n, hipStream_t s) {
     if (!post_fuses_finalize(p)) return hipErrorInvalidValue;
     dim3 grid(p.C / 16, n);
-    if (p.bf16) hipLaunchKernelGGL(post_fin_kernel<true>, grid, dim3(256), 0, s, p, f);
-    else hipLaunchKernelGGL(post_fin_kernel<false>, grid, dim3(256), 0, s, p, f);
-    return hipGetLastError();
+    if (p.bf16) return launch<post_fin_kernel<true>>(current_device(), grid, dim3(256), 0, s, p, f);
+    return launch<post_fin_kernel<false>>(current_device(), grid, dim3(256), 0, s, p, f);
 }
 
 hipError_t launch_finalize(const FinalizeParams& p, int n, hipStream_t s) {
@@ -4532,13 +4411,11 @@ hipError_t launch_finalize(const FinalizeParams& p, int n, hipStream_t s) {
     const int rpb = std::min(256, std::max(64, (p.prow + 15) / 16));
     const int zb = (p.prow + rpb - 1) / rpb;   // prow == 0: the producer already summed into acc
     dim3 grid((p.C + 63) / 64, n, zb < 1 ? 1 : zb);
-    hipLaunchKernelGGL(finalize_kernel, grid, dim3(256), 0, s, p, rpb);
-    return hipGetLastError();
+    return launch<finalize_kernel>(current_device(), grid, dim3(256), 0, s, p, rpb);
 }
 
 hipError_t launch_pixelnorm(const float* z, float* out, int n, int L, hipStream_t s) {
-    hipLaunchKernelGGL(pixelnorm_kernel, dim3(n), dim3(64), sizeof(float) * L, s, z, out, n, L);
-    return hipGetLastError();
+    return launch<pixelnorm_kernel>(current_device(), dim3(n), dim3(64), sizeof(float) * L, s, z, out, n, L);
 }
 
 hipError_t launch_dense(const float* x, const float* WT, const float* b, float* y, int n, int K, int J, int act, hipStream_t s) {
@@ -4546,21 +4423,15 @@ hipError_t launch_dense(const float* x, const float* WT, const float* b, float* 
     // LDS -> barrier -> 256-step fmaf chain round trip (two passes per layer instead of four: 11.3 -> ~7 us per layer)
     if (K % 256 || J % 4) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * (256 * 16 + 16 * 256 + 256);
-    hipLaunchKernelGGL((dense_lds_kernel<false, 16, 256>), dim3((J + 15) / 16), dim3(256), lds, s, x, WT, b, y, n, K, J, act,
-                       (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
-    return hipGetLastError();
+    return launch<dense_lds_kernel<false, 16, 256>>(current_device(), dim3((J + 15) / 16), dim3(256), lds, s, x, WT, b, y, n, K, J, act,
+                  (const float*)nullptr, (const float*)nullptr, (const int*)nullptr);
 }
 
 // the fused mapping network applies when its L/16 workgroups are certainly co-resident (see mapping_kernel)
 bool mapping_fused(int L, int device) {
     static const bool enabled = !(getenv("GSA_MAPFUSE") && atoi(getenv("GSA_MAPFUSE")) == 0);
     if (!enabled || L % 64 || L > 512 || L < 64) return false;
-    int num_cus;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        num_cus = device_cus(device);
-    }
-    return L / 16 <= num_cus / 2;
+    return L / 16 <= device_cus(device) / 2;
 }
 
 hipError_t launch_mapping(const float* z, float* const* wt, float* const* b, unsigned long long* const* ll, float* out, unsigned* ctl,
@@ -4571,34 +4442,20 @@ hipError_t launch_mapping(const float* z, float* const* wt, float* const* b, uns
     for (int i = 0; i < 8; ++i) { p.wt[i] = wt[i]; p.b[i] = b[i]; }
     p.ll[0] = ll[0]; p.ll[1] = ll[1];
     p.out = out; p.ctl = ctl; p.n = n; p.L = L;
-    auto kern = mapping_kernel;
-    static LaunchState states[kMaxDevices];
-    if (device < 0 || device >= kMaxDevices) return hipErrorInvalidDevice;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        hipError_t e = prepare_kernel(kern, states[device]);
-        if (e != hipSuccess) return e;
-    }
     const size_t lds = sizeof(float) * (size_t)(16 * (L + 4) + 16 * L + 16);
     // slices of 16-sample chunks side by side, as many as stay co-resident (the exchange spins)
-    int num_cus;
-    {
-        std::lock_guard<std::mutex> lk(g_launch_mu);
-        num_cus = device_cus(device);
-    }
-    const int slices = std::max(1, std::min(std::min((n + 15) / 16, kMapSlices), (num_cus / 2) / (L / 16)));
+    const int slices = std::max(1, std::min(std::min((n + 15) / 16, kMapSlices), (device_cus(device) / 2) / (L / 16)));
     // drop_workgroups > 0 (fault injection, tests only): the last workgroups are not launched, their columns never arrive and
     // every other workgroup's wait times out -- the condition gsa_check must report
-    hipLaunchKernelGGL(kern, dim3(std::max(1, L / 16 - drop_workgroups), slices), dim3(256), lds, s, p);
-    return hipGetLastError();
+    return launch<mapping_kernel>(device, dim3(std::max(1, L / 16 - drop_workgroups), slices), dim3(256), lds, s, p);
 }
 
 hipError_t launch_styles(const float* w, const float* avg, const float* psi, const float* WT, const float* b,
                          const int* col_layer, float* styles, int n, int K, int J, hipStream_t s) {
     if (K % 128 || J % 4) return hipErrorInvalidValue;
     const size_t lds = sizeof(float) * (128 * 64 + 16 * 128 + 128);
-    hipLaunchKernelGGL((dense_lds_kernel<true, 64, 128>), dim3((J + 63) / 64, std::min((n + 15) / 16, 8)), dim3(256), lds, s, w, WT, b, styles, n, K, J, 0, avg, psi, col_layer);
-    return hipGetLastError();
+    return launch<dense_lds_kernel<true, 64, 128>>(current_device(), dim3((J + 63) / 64, std::min((n + 15) / 16, 8)), dim3(256), lds, s, w, WT, b, styles,
+                  n, K, J, 0, avg, psi, col_layer);
 }
 
 hipError_t launch_torgb(const float* x, const Aff* aff, const float* w, const float* b, float* rgb, uint8_t* img,
@@ -4606,27 +4463,28 @@ hipError_t launch_torgb(const float* x, const Aff* aff, const float* w, const fl
     if (nc > 4 || C % 4) return hipErrorInvalidValue;
     const int HW = H * W;
     const dim3 grid((HW + 255) / 256, n);
+    const int dev = current_device();
 #define GSA_RGB(BF) \
-    if (C == 16) hipLaunchKernelGGL((torgb_direct_kernel<16, BF>), grid, dim3(256), 0, s, x, aff, w, b, rgb, img, HW, C, nc); \
-    else if (C < 16) hipLaunchKernelGGL((torgb_direct_kernel<0, BF>), grid, dim3(256), 0, s, x, aff, w, b, rgb, img, HW, C, nc); \
-    else hipLaunchKernelGGL(torgb_kernel<BF>, grid, dim3(256), 0, s, x, aff, w, b, rgb, img, HW, C, nc);
-    if (bf16) { GSA_RGB(true) } else { GSA_RGB(false) }
+    if (C == 16) return launch<torgb_direct_kernel<16, BF>>(dev, grid, dim3(256), 0, s, x, aff, w, b, rgb, img, HW, C, nc); \
+    if (C < 16) return launch<torgb_direct_kernel<0, BF>>(dev, grid, dim3(256), 0, s, x, aff, w, b, rgb, img, HW, C, nc); \
+    return launch<torgb_kernel<BF>>(dev, grid, dim3(256), 0, s, x, aff, w, b, rgb, img, HW, C, nc);
+    if (bf16) { GSA_RGB(true) }
+    GSA_RGB(false)
 #undef GSA_RGB
-    return hipGetLastError();
 }
 
 hipError_t launch_export_nchw(const float* x, const Aff* aff, float* out, int n, int H, int W, int C, int bf16, hipStream_t s) {
     const int HW = H * W;
-    if (bf16) hipLaunchKernelGGL(export_nchw_kernel<true>, dim3((HW + 63) / 64, C / 16, n), dim3(256), 0, s, x, aff, out, HW, C);
-    else hipLaunchKernelGGL(export_nchw_kernel<false>, dim3((HW + 63) / 64, C / 16, n), dim3(256), 0, s, x, aff, out, HW, C);
-    return hipGetLastError();
+    const dim3 grid((HW + 63) / 64, C / 16, n);
+    if (bf16) return launch<export_nchw_kernel<true>>(current_device(), grid, dim3(256), 0, s, x, aff, out, HW, C);
+    return launch<export_nchw_kernel<false>>(current_device(), grid, dim3(256), 0, s, x, aff, out, HW, C);
 }
 
 hipError_t launch_import_nhwc(const float* in, float* out, int n, int H, int W, int C, int bf16, hipStream_t s) {
     const int HW = H * W;
-    if (bf16) hipLaunchKernelGGL(import_nhwc_kernel<true>, dim3((HW + 63) / 64, C / 16, n), dim3(256), 0, s, in, out, HW, C);
-    else hipLaunchKernelGGL(import_nhwc_kernel<false>, dim3((HW + 63) / 64, C / 16, n), dim3(256), 0, s, in, out, HW, C);
-    return hipGetLastError();
+    const dim3 grid((HW + 63) / 64, C / 16, n);
+    if (bf16) return launch<import_nhwc_kernel<true>>(current_device(), grid, dim3(256), 0, s, in, out, HW, C);
+    return launch<import_nhwc_kernel<false>>(current_device(), grid, dim3(256), 0, s, in, out, HW, C);
 }
 
 // class pairs as packed fma in the fp32 final conv (speed only, same bits; GSA_FINAL_PK=0: the scalar chains)
@@ -4639,13 +4497,12 @@ template <int NCLS>
 static hipError_t launch_final_t(const float* src0, int C0, const float* src1, int C1, const float* wpk, const float* bias,
                                  float* logits, uint8_t* mask, int n, int H, int W, int bf16, hipStream_t s) {
     const size_t lds = sizeof(float) * 18 * 384;
-    if (bf16) hipLaunchKernelGGL((final_conv_kernel<NCLS, true>), dim3((H / 16) * (W / 16), n), dim3(256), lds, s, src0, C0, src1, C1, wpk,
-                                 bias, logits, mask, H, W, W / 16);
-    else if (NCLS % 2 == 0 && final_pk()) hipLaunchKernelGGL((final_conv_kernel<NCLS, false, true>), dim3((H / 16) * (W / 16), n), dim3(256), lds, s, src0, C0, src1, C1, wpk,
-                            bias, logits, mask, H, W, W / 16);
-    else hipLaunchKernelGGL((final_conv_kernel<NCLS, false>), dim3((H / 16) * (W / 16), n), dim3(256), lds, s, src0, C0, src1, C1, wpk,
-                            bias, logits, mask, H, W, W / 16);
-    return hipGetLastError();
+    const dim3 grid((H / 16) * (W / 16), n);
+    const int dev = current_device();
+    if (bf16) return launch<final_conv_kernel<NCLS, true>>(dev, grid, dim3(256), lds, s, src0, C0, src1, C1, wpk, bias, logits, mask, H, W, W / 16);
+    if (NCLS % 2 == 0 && final_pk())
+        return launch<final_conv_kernel<NCLS, false, true>>(dev, grid, dim3(256), lds, s, src0, C0, src1, C1, wpk, bias, logits, mask, H, W, W / 16);
+    return launch<final_conv_kernel<NCLS, false>>(dev, grid, dim3(256), lds, s, src0, C0, src1, C1, wpk, bias, logits, mask, H, W, W / 16);
 }
 
 hipError_t launch_final_conv(const float* src0, int C0, const float* src1, int C1, const float* wpk, const float* bias,
@@ -4669,7 +4526,7 @@ hipError_t launch_seg_eval(const float* logits, const int8_t* labels, int n, int
     const int HW = H * W;
     const dim3 grid(std::min((HW + 255) / 256, 1024), n);
 #define GSA_EVAL(K) \
-    if (classes == K) { hipLaunchKernelGGL(seg_eval_kernel<K>, grid, dim3(256), 0, s, logits, labels, HW, confusion, loss_fixed); return hipGetLastError(); }
+    if (classes == K) return launch<seg_eval_kernel<K>>(current_device(), grid, dim3(256), 0, s, logits, labels, HW, confusion, loss_fixed);
     GSA_EVAL(2) GSA_EVAL(3) GSA_EVAL(4) GSA_EVAL(5) GSA_EVAL(6) GSA_EVAL(7) GSA_EVAL(8)
 #undef GSA_EVAL
     return hipErrorInvalidValue;
@@ -4680,8 +4537,7 @@ hipError_t launch_fill_normal(float* out, int per_sample, int n, unsigned long l
     if (per_sample % 4 || per_sample <= 0 || n <= 0) return hipErrorInvalidValue;
     const long total = (long)n * (per_sample / 4);
     const int grid = (int)std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(fill_normal_kernel, dim3(grid), dim3(256), 0, s, out, per_sample, n, first_index, plane, seed);
-    return hipGetLastError();
+    return launch<fill_normal_kernel>(current_device(), dim3(grid), dim3(256), 0, s, out, per_sample, n, first_index, plane, seed);
 }
 
 }  // namespace gsa

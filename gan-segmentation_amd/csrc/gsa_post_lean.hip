@@ -9,7 +9,6 @@
 #include "gsa_dev.h"
 
 #include <cstdlib>
-#include <mutex>
 
 namespace gsa {
 namespace lean {
@@ -334,35 +333,22 @@ hipError_t launch_post_dma(const PostParams& p, int n, hipStream_t s) {
     PostParams q = p;
     q.row_groups = post_dma_band(p);
     const dim3 grid(post_dma_blocks(p), n);
-    static std::mutex mu;
-    static bool attr_done[64][2] = {};
     static const bool ost = !(getenv("GSA_POST_DMA_OST") && atoi(getenv("GSA_POST_DMA_OST")) == 0);
     const size_t lds = sizeof(float) * 4 * 8 * ((1024 / p.C + 2) * (p.C / 4) + 1024 / p.C / 4) * 4 + (ost ? 16384 : 0) + sizeof(unsigned long long) * 2 * p.C;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        bool& done = attr_done[dev][p.C == 32];
-        if (!done) {
-            const void* fs[4] = {reinterpret_cast<const void*>(lean::post_dma<16, false>), reinterpret_cast<const void*>(lean::post_dma<32, false>),
-                                 reinterpret_cast<const void*>(lean::post_dma<16, true>), reinterpret_cast<const void*>(lean::post_dma<32, true>)};
-            for (const void* f : fs) {
-                hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return e;
-            }
-            done = true;
-        }
+    const int dev = current_device();
+    if (!ost) {
+        if (p.C == 16) return launch<lean::post_dma<16, false>>(dev, grid, dim3(256), lds, s, q);
+        return launch<lean::post_dma<32, false>>(dev, grid, dim3(256), lds, s, q);
     }
-    if (p.C == 16) { if (ost) hipLaunchKernelGGL((lean::post_dma<16, true>), grid, dim3(256), lds, s, q); else hipLaunchKernelGGL((lean::post_dma<16, false>), grid, dim3(256), lds, s, q); }
-    else { if (ost) hipLaunchKernelGGL((lean::post_dma<32, true>), grid, dim3(256), lds, s, q); else hipLaunchKernelGGL((lean::post_dma<32, false>), grid, dim3(256), lds, s, q); }
-    return hipGetLastError();
+    if (p.C == 16) return launch<lean::post_dma<16, true>>(dev, grid, dim3(256), lds, s, q);
+    return launch<lean::post_dma<32, true>>(dev, grid, dim3(256), lds, s, q);
 }
 
 hipError_t launch_post_pk(const PostParams& q, dim3 grid, size_t lds, hipStream_t s) {
-    if (q.bf16) hipLaunchKernelGGL((lean::post_rows_pk<false, true>), grid, dim3(256), lds, s, q);
-    else if (post_pk_mode() >= 2) hipLaunchKernelGGL((lean::post_rows_pk<true, false>), grid, dim3(256), lds, s, q);
-    else hipLaunchKernelGGL((lean::post_rows_pk<false, false>), grid, dim3(256), lds, s, q);
-    return hipGetLastError();
+    const int dev = current_device();
+    if (q.bf16) return launch<lean::post_rows_pk<false, true>>(dev, grid, dim3(256), lds, s, q);
+    if (post_pk_mode() >= 2) return launch<lean::post_rows_pk<true, false>>(dev, grid, dim3(256), lds, s, q);
+    return launch<lean::post_rows_pk<false, false>>(dev, grid, dim3(256), lds, s, q);
 }
 
 }  // namespace gsa

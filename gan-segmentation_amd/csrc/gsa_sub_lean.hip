@@ -15,7 +15,6 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
 namespace gsa {
@@ -395,10 +394,6 @@ __global__ __launch_bounds__(512, 2) void subpixel_lean(ConvParams p) {
     TFLUSH(12, (unsigned long long)total_items); TFLUSH(15, 1ull);
 }
 
-constexpr int kMaxDev = 64;
-struct SubState { bool attr_done = false; };
-static std::mutex g_sub_mu;
-
 // LDS bytes of an instantiation (cnt: the three-buffer counter form)
 size_t sub_lds(const ConvParams& q, int nt, bool sc, bool aff, int kb, bool wst, bool cnt) {
     const int nblk0 = q.C0 / 16, nblk = (q.C0 + q.C1) / 16, wblk = wst ? 2 : nblk;
@@ -420,20 +415,9 @@ bool sub_counters(const ConvParams& q, int nt, bool sc, int kb, bool wst) {
 
 template <int NT, int EPI, bool SC, bool AFF, int KB, bool WST, bool CNT = false>
 hipError_t launch_k(const ConvParams& q, dim3 grid, hipStream_t s) {
-    static SubState st[kMaxDev];
-    auto kern = subpixel_lean<NT, EPI, SC, AFF, KB, WST, CNT>;
     const size_t lds = sub_lds(q, NT, SC, AFF, KB, WST, CNT);
-    if (lds > 160 * 1024 || q.device < 0 || q.device >= kMaxDev) return hipErrorInvalidValue;
-    {
-        std::lock_guard<std::mutex> lk(g_sub_mu);
-        if (!st[q.device].attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            st[q.device].attr_done = true;
-        }
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, q);
-    return hipGetLastError();
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    return launch<subpixel_lean<NT, EPI, SC, AFF, KB, WST, CNT>>(q.device, grid, dim3(512), lds, s, q);
 }
 
 template <int NT, int EPI, bool SC, bool AFF>
@@ -455,13 +439,6 @@ bool subpixel_lean_applies(const ConvParams& p, int nt, int epi, bool sc, int kb
     if (!enabled || p.bf16 || (nt != 1 && nt != 2) || (epi != EPI_RAW && epi != EPI_DEC) || (sc && epi != EPI_DEC)) return false;
     if (p.aff0 != nullptr && p.C1 != 0) return false;
     return lean::sub_lds(p, nt, sc, p.aff0 != nullptr, kb, wst, false) <= 160 * 1024;
-}
-
-const char* subpixel_lean_name(const ConvParams& p, int nt, int epi, bool sc, int kb, bool wst) {
-    static thread_local char buf[112];
-    snprintf(buf, sizeof buf, "void gsa::lean::subpixel_lean<%d, %d, %s, %s, %d, %s, %s>(gsa::ConvParams)", nt, epi, sc ? "true" : "false",
-             p.aff0 ? "true" : "false", kb, wst ? "true" : "false", lean::sub_counters(p, nt, sc, kb, wst) ? "true" : "false");
-    return buf;
 }
 
 // q: the ConvParams the subpixel_res launcher prepared (tiles_x, tiles_y, groups, total_tiles filled), grid: its grid

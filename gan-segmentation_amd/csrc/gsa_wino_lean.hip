@@ -25,7 +25,6 @@
 
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
 
 namespace gsa {
@@ -836,28 +835,10 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
     TFLUSH(12, (unsigned long long)items); TFLUSH(15, 1ull);
 }
 
-constexpr int kMaxDev = 64;
-struct LeanState { bool attr_done = false; int cus = 0; };
-static std::mutex g_mu;
-
 template <int EPI, bool AFF, bool RES, int NB, int GW, bool DB = true, int PF = 1, bool RGB = false>
 hipError_t launch_t(const ConvParams& p, int n, hipStream_t s) {
-    static LeanState st[kMaxDev];
-    auto kern = conv3x3_wino_lean<EPI, AFF, RES, NB, GW, DB, PF, RGB>;
     const size_t lds = sizeof(float) * ((DB ? 2 : 1) * IMG + GW * NB * SEG);
-    if (p.device < 0 || p.device >= kMaxDev) return hipErrorInvalidDevice;
-    int cus;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        LeanState& d = st[p.device];
-        if (!d.attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            if (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, p.device) != hipSuccess) d.cus = 256;
-            d.attr_done = true;
-        }
-        cus = d.cus;
-    }
+    const int cus = device_cus(p.device);
     ConvParams q = p;
     q.wpk = p.wino;
     q.tiles_x = p.W / 16;
@@ -871,8 +852,7 @@ hipError_t launch_t(const ConvParams& p, int n, hipStream_t s) {
     }
     // persistent workgroups: two 4-wave workgroups per CU (58 KB of LDS each) or one 8-wave workgroup (106 KB), each a contiguous tile range
     const int gx = std::min(q.total_tiles, cus * (GW == 1 ? (DB ? 2 : 3) : 1));
-    hipLaunchKernelGGL(kern, dim3(gx), dim3(256 * GW), lds, s, q);
-    return hipGetLastError();
+    return launch<conv3x3_wino_lean<EPI, AFF, RES, NB, GW, DB, PF, RGB>>(p.device, dim3(gx), dim3(256 * GW), lds, s, q);
 }
 
 // GSA_WINO_LEAN_SB=1: the single-buffered three-workgroups-per-CU form for the 16 -> 16 decoder layers (A/B; same bits)
@@ -921,23 +901,9 @@ hipError_t launch_shape(const ConvParams& p, int epi, int n, hipStream_t s) {
 
 template <int EPI, bool AFF, int NT = 1, int IL = 0>
 hipError_t launch_stream_t(const ConvParams& p, int n, hipStream_t s) {
-    static LeanState st[kMaxDev];
-    auto kern = conv3x3_wino_stream<EPI, AFF, NT, IL>;
     const int nblk = p.C0 / 16;
     const size_t lds = sizeof(float) * (2 * IMG + 2 * NT * SEG + 64 * NT + nblk * 32);
-    if (p.device < 0 || p.device >= kMaxDev) return hipErrorInvalidDevice;
-    int cus;
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        LeanState& d = st[p.device];
-        if (!d.attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-            if (hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, p.device) != hipSuccess) d.cus = 256;
-            d.attr_done = true;
-        }
-        cus = d.cus;
-    }
+    const int cus = device_cus(p.device);
     ConvParams q = p;
     q.wpk = p.wino;
     q.tiles_x = p.W / 16;
@@ -959,8 +925,7 @@ hipError_t launch_stream_t(const ConvParams& p, int n, hipStream_t s) {
     // multiple of 8 the groups of a tile range meet in one XCD's L2 (conv3x3_wino's launch shape)
     const int slots = std::max(1, cus * (NT == 1 ? 2 : 1) / q.groups);
     const int gx = std::min(q.total_tiles, slots);
-    hipLaunchKernelGGL(kern, dim3(gx, q.groups), dim3(256), lds, s, q);
-    return hipGetLastError();
+    return launch<conv3x3_wino_stream<EPI, AFF, NT, IL>>(p.device, dim3(gx, q.groups), dim3(256), lds, s, q);
 }
 
 }  // namespace lean
@@ -1011,21 +976,6 @@ int stream_interleaved() {
 #else
     return 0;
 #endif
-}
-
-const char* wino_lean_name(const ConvParams& p, int epi, int n) {
-    static thread_local char buf[112];
-    if (p.C0 >= 64) {
-        const bool pairs = stream_pairs(p, n);
-        const int il = pairs ? stream_interleaved() : 0;
-        snprintf(buf, sizeof buf, "void gsa::lean::conv3x3_wino_stream<%d, %s, %d, %d>(gsa::ConvParams)", epi, p.aff0 ? "true" : "false", pairs ? 2 : 1, il);
-        return buf;
-    }
-    const bool sb = p.C0 == 16 && epi == EPI_DEC && single_buffered();
-    const bool rgbf = p.rgb_img != nullptr;
-    snprintf(buf, sizeof buf, "void gsa::lean::conv3x3_wino_lean<%d, %s, %s, %d, %d, %s, %d, %s>(gsa::ConvParams)", epi, p.aff0 ? "true" : "false",
-             p.resid ? "true" : "false", p.C0 / 16, p.Cout / 16, sb ? "false" : "true", p.C0 == 16 && !sb && !rgbf ? prefetch_sets() : 1, rgbf ? "true" : "false");
-    return buf;
 }
 
 hipError_t launch_wino_lean(const ConvParams& p, int epi, int n, hipStream_t s) {

@@ -922,3 +922,30 @@ def test_speed_switches_do_not_change_the_bits(torch_cuda, tmp_path, env):
     script.write_text(_SWITCH_WORKER.replace("ROOT_DIR", repr(root)))
     out = subprocess.run([sys.executable, str(script)], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "SWITCH_OK" in out.stdout, "%r: %s" % (env, out.stdout[-800:] + out.stderr[-2500:])
+
+
+def test_profile_labels_are_the_launched_kernels(torch_cuda):
+    """Profile level 2 labels every entry "<kernel> | <layer>" with the kernel the launch helper actually launched, spelled as
+    rocprofv3 spells it (the demangled signature) -- never a hand-written name that can drift from the dispatch."""
+    import re
+    from tests.common import gan_setup
+    from gan_segmentation_amd.image_generator import ImageGenerator
+    old_labels = {"mapping_kernel", "pixelnorm_kernel", "dense_kernel", "styles_kernel", "post_fin_kernel<blur>", "post_fin_kernel<const>",
+                  "post_kernel<blur>", "post_kernel<const>", "finalize_kernel", "export_nchw_kernel", "torgb_direct_kernel", "torgb_kernel",
+                  "final_conv_kernel", "import_nhwc_kernel"}
+    for gan, precision in (("ffhq", "fp32"), ("cars", "bf16")):
+        gcfg, gp, dcfg, dp, z, noise = gan_setup(gan, batch=4)
+        gen = ImageGenerator.from_params(gcfg, gp, dcfg, dp, gpu_ids=[0], batch_size=4, precision=precision)
+        ctx = gen.netG._model.ctx
+        ctx.profile_enable(2)
+        ctx.profile_reset()
+        gen.generate_batch(z, noise)
+        torch_cuda.cuda.synchronize()
+        entries = ctx.profile_entries()
+        ctx.profile_enable(0)
+        assert entries, "%s %s: no profile entries" % (gan, precision)
+        for e in entries:
+            kernel, _, layer = e["name"].partition(" | ")
+            assert layer and e["launches"] >= 1, e
+            assert re.match(r"^(void )?gsa::\S.*\)$", kernel), "%s %s: %r is not a demangled gsa:: signature" % (gan, precision, e["name"])
+            assert kernel not in old_labels, e["name"]
