@@ -8,7 +8,12 @@ uint8 pairs to rank 0 per step.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the bench contract in DESIGN.md)."""
+Prints ONE JSON line on rank 0 (see the bench contract in DESIGN.md).  A plain run does only what the headline needs: set up,
+warm up, time the steps, write --dump-outputs, print the line.  --full adds everything else the line can carry: the per-kernel
+roofline pass (and --layers), the output digest against the oracle's, and at N=1 the end-to-end rates, the secondary
+configurations, the box calibration and the CPU baseline:
+
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full"""
 import argparse
 import json
 import os
@@ -512,6 +517,47 @@ def roof_seconds(entries, precision):
     return t_mfma, t_hbm
 
 
+def step_figures(entries, gan, precision, steps, batch, world, value, step_ms):
+    """--full: `roofline`, `whole_path` and `kernels` of the line from the roofline pass's per-kernel entries (sorted by time,
+    longest first) and the headline's `value` (pairs/s) and `step_ms`."""
+    top = entries[0]
+    kms = sum(e["ms"] for e in entries)
+    # FLOP the kernels really execute (Winograd forms, the sub-pixel form of nearest-x2 + conv3x3, 1x1 shortcuts at input
+    # resolution): what the MFMA roofline of the whole step is priced on
+    exec_gflop = sum(e["flops"] for e in entries) / steps / batch / 1e9
+    mfma_peak = PEAK_FP32_TFLOPS if precision == "fp32" else PEAK_BF16_TFLOPS
+    t_mfma, t_hbm = roof_seconds(entries, precision)
+    roof_ms = 1e3 * (t_mfma + t_hbm) / steps
+    return {
+        "roofline": roofline_of(top, precision, pmc_traffic(top["name"])),
+        "whole_path": {
+            # the FLOP the kernels EXECUTE per second against the f32 MFMA peak (dense bf16 peak in bf16 mode): the utilisation
+            # of the pipe over the whole step; and the step against its own strength-reduced roof
+            "executed_gflop_per_sample": round(exec_gflop, 2),
+            "executed_tflops": round(exec_gflop * value / 1e3, 2),
+            "mfma_peak_tflops": mfma_peak,
+            "frac_of_mfma_peak": round(exec_gflop * value / 1e3 / world / mfma_peak, 4),
+            "roof_ms": round(roof_ms, 3),
+            "roof_ms_mfma": round(1e3 * t_mfma / steps, 3), "roof_ms_hbm": round(1e3 * t_hbm / steps, 3),
+            "frac_of_roof": round(roof_ms / step_ms, 4),
+            "roof_note": "roof_ms = per kernel max(executed FLOP / MFMA peak, algorithmic bytes / 6.29 TB/s copy rate), summed over the step",
+            # the same step in the reference's formulation (SURVEY 8d: 2*MACs of the direct convolutions) -- a throughput, not a utilisation
+            "reference_gflop_per_sample": GFLOP_PER_SAMPLE[gan],
+            "algorithmic_tflops": round(GFLOP_PER_SAMPLE[gan] * value / 1e3, 2),
+            "algorithmic_frac": round(GFLOP_PER_SAMPLE[gan] * value / 1e3 / world / mfma_peak, 4),
+            "algorithmic_hbm_gbs": round(MB_PER_SAMPLE[gan] * value / 1e3, 1),
+            "hbm_frac_of_peak": round(MB_PER_SAMPLE[gan] * value / 1e3 / world / PEAK_HBM_GBS, 4),
+            "hbm_frac_of_measured_peak": round(MB_PER_SAMPLE[gan] * value / 1e3 / world / MEASURED_HBM_GBS, 4),
+            "kernel_ms_per_step": round(kms / steps, 3),
+        },
+        "kernels": [{"name": e["name"], "ms_per_step": round(e["ms"] / steps, 3),
+                     "executed_tflops": round(e["flops"] / (e["ms"] * 1e-3) / 1e12, 2) if e["ms"] > 0 else 0.0,
+                     "algorithmic_tflops": round(e["alg_flops"] / (e["ms"] * 1e-3) / 1e12, 2) if e["ms"] > 0 else 0.0,
+                     "gbs": round(e["bytes"] / (e["ms"] * 1e-3) / 1e9, 1) if e["ms"] > 0 else 0.0}
+                    for e in entries[:8]],
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -528,13 +574,17 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16"),
                     help="bf16 = bf16 MFMA operands, fp32 accumulate/statistics (BASELINE.json configs[4]); "
                          "the headline metric is fp32")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline pass (roofline, whole_path, kernels), the output digest against the oracle's "
+                         "(output) and, at N=1, end_to_end, secondary, box and cpu_baseline (default: off, the line carries the headline only)")
     ap.add_argument("--job-samples", type=int, default=2000,
-                    help="samples of the `main.py generate` job timed under end_to_end (batch 32, files on disk; 0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short measurements of configs[3]/[4] and the end-to-end rate")
+                    help="--full: samples of the `main.py generate` job timed under end_to_end (batch 32, files on disk; 0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full: skip the short measurements of configs[3]/[4], the end-to-end rate and the box calibration")
     ap.add_argument("--allow-blocking", action="store_true",
                     help="N>1: fall back to the blocking gather if the overlapped one is refused (default: exit non-zero)")
-    ap.add_argument("--layers", action="store_true", help="per-layer kernel breakdown on stderr")
+    ap.add_argument("--layers", action="store_true", help="--full: per-layer kernel breakdown of the roofline pass on stderr")
     ap.add_argument("--stub-producer", action="store_true",
                     help="CPU rehearsal of the N-rank control flow: gloo, deterministic uint8 pairs instead of the kernels "
                          "(the line says data: stub and is not a measurement)")
@@ -542,6 +592,8 @@ def main():
                     help="after the timed steps, write what the last one returned to its caller (rank 0: the gathered image and mask "
                          "of every rank) as DIR/image.npy and DIR/mask.npy, float32, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
+    if args.layers and not args.full:
+        ap.error("--layers prints the roofline pass, which only --full runs: add --full")
     t_proc = time.perf_counter()
 
     if args.gpus > 1 and not os.environ.get("WORLD_SIZE"):
@@ -649,38 +701,28 @@ def main():
         parts = gat.result(last_slot) if state["gather"] != "blocking" else [gen.generate_batch(z, noise)]
         dumped = dump_outputs(args.dump_outputs, {"image": torch.cat([p[0] for p in parts]).cpu().numpy(),
                                                   "mask": torch.cat([p[1] for p in parts]).cpu().numpy()})
-    # ---- roofline pass (untimed): the same K steps with every launch bracketed by HIP events on its
+    # ---- roofline pass (--full, untimed): the same K steps with every launch bracketed by HIP events on its
     # stream, and with the decoder/synthesis stream overlap off, so that a kernel's duration is its own
     # and not stretched by the kernel running beside it
-    t1 = time.perf_counter()
-    ctx.set_overlap(0)
-    ctx.profile_enable(2 if args.layers else 1)
-    ctx.profile_reset()
-    for _ in range(args.steps):
-        gen.generate_batch(z, noise)
-    torch.cuda.synchronize()
-    entries = ctx.profile_entries()
-    ctx.profile_enable(0)
-    ctx.set_overlap(-1)        # back to the default (by batch size)
-    t_prof = time.perf_counter() - t1
+    if args.full:
+        t1 = time.perf_counter()
+        ctx.set_overlap(0)
+        ctx.profile_enable(2 if args.layers else 1)
+        ctx.profile_reset()
+        for _ in range(args.steps):
+            gen.generate_batch(z, noise)
+        torch.cuda.synchronize()
+        entries = ctx.profile_entries()
+        ctx.profile_enable(0)
+        ctx.set_overlap(-1)        # back to the default (by batch size)
+        t_prof = time.perf_counter() - t1
     dts = [loop.max_over_ranks(d) for d in timing["dts_local"]]      # per region: the slowest rank
     dt = median(dts)
 
     if rank == 0:
         pairs = world * B * args.steps
         value = pairs / dt
-        entries.sort(key=lambda e: -e["ms"])
-        top = entries[0]
-        kms = sum(e["ms"] for e in entries)
-        # FLOP the kernels really execute (Winograd forms, the sub-pixel form of nearest-x2 + conv3x3, 1x1 shortcuts at input
-        # resolution): what the MFMA roofline of the whole step is priced on
-        exec_gflop = sum(e["flops"] for e in entries) / args.steps / B / 1e9
-        roofline = roofline_of(top, args.precision, pmc_traffic(top["name"]))
-        mfma_peak = PEAK_FP32_TFLOPS if args.precision == "fp32" else PEAK_BF16_TFLOPS
-        t_mfma, t_hbm = roof_seconds(entries, args.precision)
-        roof_ms = 1e3 * (t_mfma + t_hbm) / args.steps
         step_ms = 1e3 * dt / args.steps
-        out_img, out_mask = gat.buffers(last_slot) if state["gather"] != "blocking" else gen.generate_batch(z, noise)
         out = {
             "metric": "synthetic (image,mask) pairs/sec, %s-%d StyleGAN+decoder" % (args.gan.upper(), 2 ** mr),
             "value": round(value, 3), "unit": "pairs/s", "n_gpus": world, "ranks": ranks, "devices": devices, "launcher": launcher,
@@ -702,44 +744,22 @@ def main():
                        "gather": state["gather"],
                        "backend": dist.get_backend() if ranks > 1 else "none",
                        "graph": "eager (GSA_GRAPH=%s)" % os.environ.get("GSA_GRAPH", "")},
-            "roofline": roofline,
-            "whole_path": {
-                # the FLOP the kernels EXECUTE per second against the f32 MFMA peak (dense bf16 peak in bf16 mode): the utilisation
-                # of the pipe over the whole step; and the step against its own strength-reduced roof
-                "executed_gflop_per_sample": round(exec_gflop, 2),
-                "executed_tflops": round(exec_gflop * value / 1e3, 2),
-                "mfma_peak_tflops": mfma_peak,
-                "frac_of_mfma_peak": round(exec_gflop * value / 1e3 / world / mfma_peak, 4),
-                "roof_ms": round(roof_ms, 3),
-                "roof_ms_mfma": round(1e3 * t_mfma / args.steps, 3), "roof_ms_hbm": round(1e3 * t_hbm / args.steps, 3),
-                "frac_of_roof": round(roof_ms / step_ms, 4),
-                "roof_note": "roof_ms = per kernel max(executed FLOP / MFMA peak, algorithmic bytes / 6.29 TB/s copy rate), summed over the step",
-                # the same step in the reference's formulation (2*MACs of the direct convolutions) -- a throughput, not a utilisation
-                "reference_gflop_per_sample": GFLOP_PER_SAMPLE[args.gan],
-                "algorithmic_tflops": round(GFLOP_PER_SAMPLE[args.gan] * value / 1e3, 2),
-                "algorithmic_frac": round(GFLOP_PER_SAMPLE[args.gan] * value / 1e3 / world / mfma_peak, 4),
-                "algorithmic_hbm_gbs": round(MB_PER_SAMPLE[args.gan] * value / 1e3, 1),
-                "hbm_frac_of_peak": round(MB_PER_SAMPLE[args.gan] * value / 1e3 / world / PEAK_HBM_GBS, 4),
-                "hbm_frac_of_measured_peak": round(MB_PER_SAMPLE[args.gan] * value / 1e3 / world / MEASURED_HBM_GBS, 4),
-                "kernel_ms_per_step": round(kms / args.steps, 3),
-            },
-            # the bytes the timed configuration produced (rank 0, sample 0 of the last timed step) against the C oracle
-            "output": output_check(args.gan, B, args.precision, out_img, out_mask),
-            "kernels": [{"name": e["name"], "ms_per_step": round(e["ms"] / args.steps, 3),
-                         "executed_tflops": round(e["flops"] / (e["ms"] * 1e-3) / 1e12, 2) if e["ms"] > 0 else 0.0,
-                         "algorithmic_tflops": round(e["alg_flops"] / (e["ms"] * 1e-3) / 1e12, 2) if e["ms"] > 0 else 0.0,
-                         "gbs": round(e["bytes"] / (e["ms"] * 1e-3) / 1e9, 1) if e["ms"] > 0 else 0.0}
-                        for e in entries[:8]],
         }
-        if args.layers:
-            for e in entries:
-                print("%-70s %8.3f ms/step %7.2f TF/s executed (%7.2f algorithmic) %8.1f GB/s" % (
-                    e["name"], e["ms"] / args.steps, e["flops"] / (e["ms"] * 1e-3) / 1e12 if e["ms"] else 0,
-                    e["alg_flops"] / (e["ms"] * 1e-3) / 1e12 if e["ms"] else 0,
-                    e["bytes"] / (e["ms"] * 1e-3) / 1e9 if e["ms"] else 0), file=sys.stderr)
-        wall = {"setup": round(t_setup, 2), "warmup": round(t_warm, 3), "timed": round(sum(dts), 4), "timed_median_region": round(dt, 4),
-                "profile_pass": round(t_prof, 3)}
-        if world == 1 and not args.no_secondary:
+        wall = {"setup": round(t_setup, 2), "warmup": round(t_warm, 3), "timed": round(sum(dts), 4), "timed_median_region": round(dt, 4)}
+        if args.full:
+            entries.sort(key=lambda e: -e["ms"])
+            out.update(step_figures(entries, args.gan, args.precision, args.steps, B, world, value, step_ms))
+            # the bytes the timed configuration produced (rank 0, sample 0 of the last timed step) against the C oracle
+            out_img, out_mask = gat.buffers(last_slot) if state["gather"] != "blocking" else gen.generate_batch(z, noise)
+            out["output"] = output_check(args.gan, B, args.precision, out_img, out_mask)
+            if args.layers:
+                for e in entries:
+                    print("%-70s %8.3f ms/step %7.2f TF/s executed (%7.2f algorithmic) %8.1f GB/s" % (
+                        e["name"], e["ms"] / args.steps, e["flops"] / (e["ms"] * 1e-3) / 1e12 if e["ms"] else 0,
+                        e["alg_flops"] / (e["ms"] * 1e-3) / 1e12 if e["ms"] else 0,
+                        e["bytes"] / (e["ms"] * 1e-3) / 1e9 if e["ms"] else 0), file=sys.stderr)
+            wall["profile_pass"] = round(t_prof, 3)
+        if args.full and world == 1 and not args.no_secondary:
             t1 = time.perf_counter()
             out["end_to_end"] = measure_end_to_end(gen, B, max(4, min(args.steps, 20)), dev)
             if args.gan == "ffhq" and args.precision == "fp32" and args.job_samples > 0:
@@ -762,7 +782,7 @@ def main():
             except Exception as e:      # calibration only: never costs the line
                 out["box"] = {"error": "%s: %s" % (type(e).__name__, e)}
             wall["secondary"] = round(time.perf_counter() - t1, 2)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             t1 = time.perf_counter()
             out["cpu_baseline"] = cpu_baseline(args.gan)
             wall["cpu_baseline"] = round(time.perf_counter() - t1, 2)

@@ -3,7 +3,7 @@
 
     python tests/golden/make_bench_hash.py
 
-bench.py prints the same digest of what the HIP path produced in its timed configuration and says whether it
+bench.py --full prints the same digest of what the HIP path produced in its timed configuration and says whether it
 matches; tests/test_gpu_parity.py asserts it on the GPU, tests/test_oracle.py re-derives one entry on the CPU.
 Inputs = bench.py's: synthetic weights (seeds 2 / 3), W.synthetic_inputs(gcfg, batch, seed_z=1000+rank,
 seed_noise=2000+rank) with rank 0.  fp32 configurations only (bf16 mode is a stated tolerance, not bit equality).

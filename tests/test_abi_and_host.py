@@ -571,6 +571,37 @@ def test_bench_under_torchrun_is_unchanged_and_a_dead_rank_fails_the_run():
         assert "stopping the other ranks" in bad.stderr or "needs a HIP device" in bad.stderr
 
 
+def test_bench_layers_needs_full():
+    """--layers prints the roofline pass, which only --full runs: without --full it is refused before anything starts."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layers", "--steps", "1"],
+                         capture_output=True, text=True, timeout=120, env=_bench_env())
+    assert out.returncode == 2 and "{" not in out.stdout and "add --full" in out.stderr, out.stderr[-1000:]
+
+
+_FULL_ONLY = ("roofline", "whole_path", "kernels", "output", "end_to_end", "secondary", "box", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest(torch_cuda):
+    """A plain run prints the headline only (no roofline pass, no oracle digest, no side measurements); --full adds the
+    roofline pass and the output check, and the output of the timed configuration equals the oracle's."""
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--settle-steps", "0"]
+    plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common,
+                           capture_output=True, text=True, timeout=300, env=_bench_env())
+    assert plain.returncode == 0, plain.stdout[-2000:] + plain.stderr[-3000:]
+    line = _one_json_line(plain.stdout)
+    assert line["unit"] == "pairs/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 2 and line["warmup"] == 1
+    assert not any(k in line for k in _FULL_ONLY) and "profile_pass" not in line["wall_s"], sorted(line)
+    full = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + ["--full", "--no-secondary", "--no-cpu-baseline"],
+                          capture_output=True, text=True, timeout=300, env=_bench_env())
+    assert full.returncode == 0, full.stdout[-2000:] + full.stderr[-3000:]
+    line = _one_json_line(full.stdout)
+    assert all(k in line for k in ("roofline", "whole_path", "kernels", "output")) and "profile_pass" in line["wall_s"]
+    assert line["output"]["matches_oracle"] is True and 0.0 < line["roofline"]["frac"] <= 1.0
+    assert not any(k in line for k in ("end_to_end", "secondary", "box", "cpu_baseline"))
+
+
 def test_bench_roofline_fields_are_fractions():
     """`roofline.frac` is what the pipe does: executed FLOP / time / peak for an MFMA-bound kernel, algorithmic bytes / time /
     8 TB/s for an HBM-bound one -- never the reference-formulation throughput, which moved to algorithmic_*."""

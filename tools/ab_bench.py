@@ -7,7 +7,7 @@ import subprocess
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for name in sys.argv[1:]:
-    code = ("import os, sys; sys.path.insert(0, %r); sys.argv = ['bench.py', '--steps', '20', '--warmup', '3', '--layers', "
+    code = ("import os, sys; sys.path.insert(0, %r); sys.argv = ['bench.py', '--steps', '20', '--warmup', '3', '--full', '--layers', "
             "'--no-cpu-baseline', '--no-secondary']; import torch; from gan_segmentation_amd import _lib; "
             "_lib.HIP_LIBRARY = os.path.join(os.path.dirname(_lib.HIP_LIBRARY), %r); import bench; bench.main()" % (ROOT, name))
     tag = name.replace(".so", "")

@@ -1,13 +1,16 @@
 #!/bin/bash
-# Diagnostic PMC pass: dynamic instruction counts per kernel (scalar / vector / branch ...) over one bench step; run on the GPU box via gpurun.
+# Diagnostic PMC pass: dynamic instruction counts per kernel (scalar / vector / branch ...) over one bench step; run on the GPU box.
+# Files under ${RESULTS_DIR:-results}/pmcinst.
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/pmcinst
-GSA_SIDE_LEVELS=0 timeout -k 10 280 rocprofv3 --pmc SQ_WAVES SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d gpurun_out/pmcinst -o insts -- python bench.py --steps 1 --warmup 1 --settle-steps 0 --no-cpu-baseline --no-secondary > gpurun_out/pmcinst/insts.json 2> gpurun_out/pmcinst/insts.err; echo "insts rc=$?"
-python3 - <<'PY'
-import collections, csv
+dir=${RESULTS_DIR:-results}/pmcinst
+mkdir -p $dir
+# --full: the summary below keeps the last of the 3 steps (warm-up, timed step, roofline-pass step)
+GSA_SIDE_LEVELS=0 timeout -k 10 280 rocprofv3 --pmc SQ_WAVES SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_BRANCH SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --kernel-trace --output-format csv -d $dir -o insts -- python bench.py --steps 1 --warmup 1 --settle-steps 0 --repeats 1 --full --no-cpu-baseline --no-secondary > $dir/insts.json 2> $dir/insts.err; echo "insts rc=$?"
+python3 - "$dir" <<'PY'
+import collections, csv, sys
 rows = collections.OrderedDict()
-for r in csv.DictReader(open("gpurun_out/pmcinst/insts_counter_collection.csv")):
+for r in csv.DictReader(open(sys.argv[1] + "/insts_counter_collection.csv")):
     if "gsa::" not in r["Kernel_Name"]:
         continue
     k = int(r["Dispatch_Id"])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Summarises the PMC passes of tools/pmc.sh (gpurun_out/pmc/*_counter_collection.csv) per kernel
+"""Summarises the PMC passes of tools/pmc.sh (results/pmc/*_counter_collection.csv by default) per kernel
 symbol over the LAST timed bench step and writes profiles/<tag>_pmc_summary.json.
 
 FETCH_SIZE is doubled (gfx950 reports half the bytes of wide coalesced reads -- MI355X_MICROARCH.md
@@ -9,7 +9,7 @@ import csv
 import json
 import sys
 
-d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+d = sys.argv[1] if len(sys.argv) > 1 else "results/pmc"
 tag = sys.argv[2] if len(sys.argv) > 2 else "r01"
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel sums of the tools/pmc_sq.sh passes (last bench step)."""
 import collections, csv, sys
-d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmcsq"
+d = sys.argv[1] if len(sys.argv) > 1 else "results/pmcsq"
 agg = collections.OrderedDict()
 for name in ("vmem", "lds", "act"):
     rows = collections.OrderedDict()
