@@ -24,6 +24,7 @@ API_SYMBOLS = (
     "generator_forward", "decoder_forward", "generate", "set_overlap", "set_precision", "segmentation_eval", "fill_inputs",
     "profile_enable", "profile_collect",
     "profile_entry", "profile_reset", "version", "check", "status_snapshot", "debug_inject",
+    "mapping_forward", "generator_forward_w", "generate_w",
 )
 
 
@@ -77,6 +78,9 @@ class Api:
             "generator_forward": (c.c_int, [vp, vp, i32, vp, c.POINTER(vp), i32, vp, vp, c.POINTER(vp), i32]),
             "decoder_forward": (c.c_int, [vp, vp, i32, c.POINTER(vp), i32, vp, vp]),
             "generate": (c.c_int, [vp, vp, i32, vp, c.POINTER(vp), i32, vp, vp]),
+            "mapping_forward": (c.c_int, [vp, vp, i32, vp, vp]),
+            "generator_forward_w": (c.c_int, [vp, vp, i32, vp, i32, c.POINTER(vp), i32, vp, vp, c.POINTER(vp), i32]),
+            "generate_w": (c.c_int, [vp, vp, i32, vp, i32, c.POINTER(vp), i32, vp, vp]),
             "set_overlap": (c.c_int, [vp, i32]),
             "set_precision": (c.c_int, [vp, i32]),
             "segmentation_eval": (c.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
@@ -247,6 +251,24 @@ class Context:
 
     def generate(self, stream, n, z, noise, img, mask):
         self._check(self.api.generate(self._h, stream, n, z, _ptr_array(noise), len(noise), img, mask), "generate")
+        self._after_step()
+
+    def mapping_forward(self, stream, n, z, w):
+        """gsa_mapping_forward: z (n, latent) -> the untruncated w (n, latent), into the caller's buffer."""
+        self._check(self.api.mapping_forward(self._h, stream, n, z, w), "mapping_forward")
+        self._after_step()
+
+    def generator_forward_w(self, stream, n, dlatents, num_layers, noise, rgb=None, img=None, feats=None):
+        """gsa_generator_forward_w: generator_forward from per-layer dlatents (n, num_layers, latent)."""
+        fp = _ptr_array(feats) if feats is not None else None
+        self._check(self.api.generator_forward_w(self._h, stream, n, dlatents, num_layers, _ptr_array(noise), len(noise), rgb, img, fp,
+                                                 len(feats) if feats is not None else 0), "generator_forward_w")
+        self._after_step()
+
+    def generate_w(self, stream, n, dlatents, num_layers, noise, img, mask):
+        """gsa_generate_w: the fused step from per-layer dlatents."""
+        self._check(self.api.generate_w(self._h, stream, n, dlatents, num_layers, _ptr_array(noise), len(noise), img, mask),
+                    "generate_w")
         self._after_step()
 
     def set_precision(self, precision):

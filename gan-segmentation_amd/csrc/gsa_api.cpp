@@ -90,6 +90,8 @@ struct gsa_ctx {
     float *style_wt = nullptr, *style_b = nullptr;
     int* style_col_layer = nullptr;
     int style_cols = 0;
+    int4* style_tiles = nullptr;            // per-layer dlatents path: {layer, first column, columns <= 64, 0} per workgroup
+    int style_num_tiles = 0;
     GenBlockDev blk[kMaxLevels];
     float *rgb_w = nullptr, *rgb_b = nullptr;
 
@@ -754,6 +756,20 @@ int gsa_generator_commit(gsa_ctx* c) {
         c->style_col_layer = (int*)d;
     }
     {
+        // workgroups of the dlatents style kernel: each holds up to 64 columns of ONE layer (layer l = 2*level + k, 2C columns from style_off)
+        std::vector<int4> tiles;
+        for (int l = 0; l < c->nlev; ++l)
+            for (int k = 0; k < 2; ++k)
+                for (int c0 = 0; c0 < 2 * c->blk[l].C; c0 += 64)
+                    tiles.push_back(make_int4(2 * l + k, c->blk[l].style_off[k] + c0, std::min(64, 2 * c->blk[l].C - c0), 0));
+        void* d = nullptr;
+        HIP_TRY(hipMalloc(&d, sizeof(int4) * tiles.size()));
+        T.push_back(d);
+        HIP_TRY(hipMemcpy(d, tiles.data(), sizeof(int4) * tiles.size(), hipMemcpyHostToDevice));
+        c->style_tiles = (int4*)d;
+        c->style_num_tiles = (int)tiles.size();
+    }
+    {
         const int R = 1 << c->gc.max_res_log2, C = c->ch[c->nlev - 1], nc = c->gc.channels;
         snprintf(nm, sizeof nm, "%d_conv_to_rgb", R);
         if (int rc = get_std(c, nm, &std)) return rc;
@@ -1013,14 +1029,16 @@ int gsa_reserve(gsa_ctx* c, int32_t max_batch) {
 
 // ------------------------------------------------------------------------ forward passes
 
-static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* const* noise, float* rgb,
+static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* dl, const float* const* noise, float* rgb,
                               uint8_t* img, float* const* feats, bool record_levels);
 
 // The statistics rely on `partials` / `stat_acc` / the tickets being all zero between layers (the producers ADD to their rows,
 // finalize_kernel clears what it read).  A pass that fails between a producer and its finalize (a launch error, a null noise
 // plane) would leave rows dirty and every later pass of the context would add them into its instance-norm sums: the context
 // remembers that a pass did not complete and the next one re-zeroes the three buffers on its stream first.
-static int run_generator(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* const* noise, float* rgb,
+// The input is either z (N, latent_size) -- mapping network, then the styles from one w row per sample -- or, with z null, the
+// untruncated per-layer dlatents dl (N, 2*nlev, latent_size), whose styles take layer l's row for layer l's columns.
+static int run_generator(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* dl, const float* const* noise, float* rgb,
                          uint8_t* img, float* const* feats, bool record_levels = false) {
     if (c->stats_dirty) {
         HIP_TRY(hipMemsetAsync(c->partials, 0, c->partials_bytes, s));
@@ -1028,7 +1046,7 @@ static int run_generator(gsa_ctx* c, hipStream_t s, int n, const float* z, const
         HIP_TRY(hipMemsetAsync(c->stat_tickets, 0, c->ticket_bytes, s));
     }
     c->stats_dirty = true;
-    const int rc = run_generator_pass(c, s, n, z, noise, rgb, img, feats, record_levels);
+    const int rc = run_generator_pass(c, s, n, z, dl, noise, rgb, img, feats, record_levels);
     if (rc == GSA_OK) c->stats_dirty = false;
     if (rc == GSA_OK && c->fault_range_after >= 0 && c->fault_range_after-- == 0) {
         // test hook: from this pass on the statistics-range word reads as if an instance norm had overflowed (it is sticky)
@@ -1037,27 +1055,41 @@ static int run_generator(gsa_ctx* c, hipStream_t s, int n, const float* z, const
     return rc;
 }
 
-static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* const* noise, float* rgb,
-                              uint8_t* img, float* const* feats, bool record_levels) {
-    const int L = c->gc.latent_size, nlev = c->nlev;
+// mapping network: PixelNorm, 8 x (dense + LeakyReLU) of z into w (N, latent_size); the fallback chain ping-pongs through lat[0/1]
+// and writes its last layer to w (lat[0] for the forward pass: the same buffers as always)
+static int run_mapping(gsa_ctx* c, hipStream_t s, int n, const float* z, float* w) {
+    const int L = c->gc.latent_size;
     const double N = n;
-    // mapping network: PixelNorm, 8 x (dense + LeakyReLU)
-    int cur = 0;
     if (mapping_fused(L, c->device)) {
         Launch lp(c, s, "g.mapping", 3.0 * N * L + 16.0 * N * L * L, 4.0 * (8.0 * L * (double)L + 18 * N * L));
-        HIP_TRY(launch_mapping(z, c->map_wt, c->map_b, c->map_ll, c->lat[0], c->map_ctl, n, L, c->device, s, c->fault == 1 ? 1 : 0));
+        HIP_TRY(launch_mapping(z, c->map_wt, c->map_b, c->map_ll, w, c->map_ctl, n, L, c->device, s, c->fault == 1 ? 1 : 0));
     } else {
         { Launch lp(c, s, "g.mapping.pixelnorm", 3.0 * N * L, 8.0 * N * L);
           HIP_TRY(launch_pixelnorm(z, c->lat[0], n, L, s)); }
+        int cur = 0;
         for (int i = 0; i < 8; ++i) {
             Launch lp(c, s, "g.mapping.dense", 2.0 * N * L * L, 4.0 * (L * (double)L + 2 * N * L));
-            HIP_TRY(launch_dense(c->lat[cur], c->map_wt[i], c->map_b[i], c->lat[cur ^ 1], n, L, L, 1, s));
+            HIP_TRY(launch_dense(c->lat[cur], c->map_wt[i], c->map_b[i], i == 7 ? w : c->lat[cur ^ 1], n, L, L, 1, s));
             cur ^= 1;
         }
     }
-    const float* w = c->lat[cur];
-    { Launch lp(c, s, "g.styles", 2.0 * N * L * c->style_cols, 4.0 * ((double)L * c->style_cols + N * c->style_cols));
-      HIP_TRY(launch_styles(w, c->latent_avg, c->psi, c->style_wt, c->style_b, c->style_col_layer, c->styles, n, L, c->style_cols, s)); }
+    return GSA_OK;
+}
+
+static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* dl, const float* const* noise, float* rgb,
+                              uint8_t* img, float* const* feats, bool record_levels) {
+    const int L = c->gc.latent_size, nlev = c->nlev;
+    const double N = n;
+    if (z) {
+        if (int rc = run_mapping(c, s, n, z, c->lat[0])) return rc;
+        const float* w = c->lat[0];
+        Launch lp(c, s, "g.styles", 2.0 * N * L * c->style_cols, 4.0 * ((double)L * c->style_cols + N * c->style_cols));
+        HIP_TRY(launch_styles(w, c->latent_avg, c->psi, c->style_wt, c->style_b, c->style_col_layer, c->styles, n, L, c->style_cols, s));
+    } else {
+        Launch lp(c, s, "g.styles", 2.0 * N * L * c->style_cols, 4.0 * ((double)L * c->style_cols + N * 2 * nlev * L + N * c->style_cols));
+        HIP_TRY(launch_styles_dlatents(dl, c->latent_avg, c->psi, c->style_wt, c->style_b, c->style_tiles, c->style_num_tiles, c->styles, n, L,
+                                       c->style_cols, 2 * nlev, s));
+    }
 
     char layer[64];
     for (int l = 0; l < nlev; ++l) {
@@ -1258,16 +1290,47 @@ static int check_batch(gsa_ctx* c, int n) {
     return GSA_OK;
 }
 
+// the dlatents entries: (N, num_layers, latent_size) with num_layers = the generator's 2*nlev style layers
+static int check_dlatents(gsa_ctx* c, const float* dl, int32_t num_layers) {
+    if (!dl) return fail(c, GSA_ERR_INVALID, "dlatents must not be null");
+    if (num_layers != 2 * c->nlev)
+        return fail(c, GSA_ERR_INVALID, "dlatents with %d layers passed, this generator has %d", num_layers, 2 * c->nlev);
+    return GSA_OK;
+}
+
+static int generator_forward(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* dl, const float* const* noise,
+                             int32_t num_noise, float* rgb, uint8_t* img, float* const* feats, int32_t num_feats) {
+    if (!noise) return fail(c, GSA_ERR_INVALID, "noise must not be null");
+    if (num_noise != 2 * c->nlev) return fail(c, GSA_ERR_INVALID, "%d noise planes passed, this generator has %d", num_noise, 2 * c->nlev);
+    if (feats && num_feats != c->nlev) return fail(c, GSA_ERR_INVALID, "%d feature pointers passed, this generator yields %d", num_feats, c->nlev);
+    if (int rc = check_batch(c, n)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return run_generator(c, (hipStream_t)stream, n, z, dl, noise, rgb, img, feats);
+}
+
 int gsa_generator_forward(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* const* noise, int32_t num_noise,
                           float* rgb, uint8_t* img, float* const* feats, int32_t num_feats) {
     if (!c) return GSA_ERR_INVALID;
     if (!c->g_ready) return fail(c, GSA_ERR_STATE, "gsa_generator_commit first");
     if (!z || !noise) return fail(c, GSA_ERR_INVALID, "z and noise must not be null");
-    if (num_noise != 2 * c->nlev) return fail(c, GSA_ERR_INVALID, "%d noise planes passed, this generator has %d", num_noise, 2 * c->nlev);
-    if (feats && num_feats != c->nlev) return fail(c, GSA_ERR_INVALID, "%d feature pointers passed, this generator yields %d", num_feats, c->nlev);
+    return generator_forward(c, stream, n, z, nullptr, noise, num_noise, rgb, img, feats, num_feats);
+}
+
+int gsa_generator_forward_w(gsa_ctx* c, void* stream, int32_t n, const float* dlatents, int32_t num_layers, const float* const* noise,
+                            int32_t num_noise, float* rgb, uint8_t* img, float* const* feats, int32_t num_feats) {
+    if (!c) return GSA_ERR_INVALID;
+    if (!c->g_ready) return fail(c, GSA_ERR_STATE, "gsa_generator_commit first");
+    if (int rc = check_dlatents(c, dlatents, num_layers)) return rc;
+    return generator_forward(c, stream, n, nullptr, dlatents, noise, num_noise, rgb, img, feats, num_feats);
+}
+
+int gsa_mapping_forward(gsa_ctx* c, void* stream, int32_t n, const float* z, float* w) {
+    if (!c) return GSA_ERR_INVALID;
+    if (!c->g_ready) return fail(c, GSA_ERR_STATE, "gsa_generator_commit first");
+    if (!z || !w) return fail(c, GSA_ERR_INVALID, "z and w must not be null");
     if (int rc = check_batch(c, n)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    return run_generator(c, (hipStream_t)stream, n, z, noise, rgb, img, feats);
+    return run_mapping(c, (hipStream_t)stream, n, z, w);
 }
 
 int gsa_decoder_forward(gsa_ctx* c, void* stream, int32_t n, const float* const* feats, int32_t num_feats, float* logits, uint8_t* mask) {
@@ -1289,11 +1352,9 @@ int gsa_decoder_forward(gsa_ctx* c, void* stream, int32_t n, const float* const*
     return run_decoder(c, s, n, fsrc, nullptr, logits, mask);
 }
 
-int gsa_generate(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* const* noise, int32_t num_noise, uint8_t* img,
-                 uint8_t* mask) {
-    if (!c) return GSA_ERR_INVALID;
-    if (!c->g_ready || !c->d_ready) return fail(c, GSA_ERR_STATE, "commit both generator and decoder first");
-    if (!z || !noise) return fail(c, GSA_ERR_INVALID, "z and noise must not be null");
+static int generate(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* dl, const float* const* noise, int32_t num_noise,
+                    uint8_t* img, uint8_t* mask) {
+    if (!noise) return fail(c, GSA_ERR_INVALID, "noise must not be null");
     if (num_noise != 2 * c->nlev) return fail(c, GSA_ERR_INVALID, "%d noise planes passed, this generator has %d", num_noise, 2 * c->nlev);
     if (c->d_n != c->nlev) return fail(c, GSA_ERR_INVALID, "decoder expects %d features, the generator yields %d", c->d_n, c->nlev);
     for (int l = 0; l < c->nlev; ++l)
@@ -1326,13 +1387,29 @@ int gsa_generate(gsa_ctx* c, void* stream, int32_t n, const float* z, const floa
         ConvParams cp = cvt_params(c, last, fsrc[last], faff[last]);
         fuse_rgb = conv_fuses_torgb(cp, EPI_DEC, false, c->gc.channels);
     }
-    if (int rc = run_generator(c, s, n, z, noise, nullptr, fuse_rgb ? nullptr : img, nullptr, ns > 0)) return rc;
+    if (int rc = run_generator(c, s, n, z, dl, noise, nullptr, fuse_rgb ? nullptr : img, nullptr, ns > 0)) return rc;
     if (ns > 0) {
         if (int rc = run_decoder(c, c->side, n, fsrc, faff, nullptr, nullptr, 0, ns, true)) return rc;
         HIP_TRY(hipEventRecord(c->ev_join, c->side));
         HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
     }
     return run_decoder(c, s, n, fsrc, faff, nullptr, mask, ns, -1, false, fuse_rgb ? img : nullptr);
+}
+
+int gsa_generate(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* const* noise, int32_t num_noise, uint8_t* img,
+                 uint8_t* mask) {
+    if (!c) return GSA_ERR_INVALID;
+    if (!c->g_ready || !c->d_ready) return fail(c, GSA_ERR_STATE, "commit both generator and decoder first");
+    if (!z || !noise) return fail(c, GSA_ERR_INVALID, "z and noise must not be null");
+    return generate(c, stream, n, z, nullptr, noise, num_noise, img, mask);
+}
+
+int gsa_generate_w(gsa_ctx* c, void* stream, int32_t n, const float* dlatents, int32_t num_layers, const float* const* noise,
+                   int32_t num_noise, uint8_t* img, uint8_t* mask) {
+    if (!c) return GSA_ERR_INVALID;
+    if (!c->g_ready || !c->d_ready) return fail(c, GSA_ERR_STATE, "commit both generator and decoder first");
+    if (int rc = check_dlatents(c, dlatents, num_layers)) return rc;
+    return generate(c, stream, n, nullptr, dlatents, noise, num_noise, img, mask);
 }
 
 int gsa_fill_inputs(gsa_ctx* c, void* stream, int32_t n, uint64_t seed, uint64_t first_index, float* z, float* const* noise,

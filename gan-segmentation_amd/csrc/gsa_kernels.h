@@ -129,6 +129,9 @@ hipError_t launch_dense(const float* x, const float* WT, const float* b, float* 
                         int lrelu, hipStream_t s);
 hipError_t launch_styles(const float* w, const float* avg, const float* psi, const float* WT, const float* b,
                          const int* col_layer, float* styles, int n, int K, int J, hipStream_t s);
+// gsa_wspace.hip: the same styles from per-layer dlatents (N, NL, K); tiles[i] = {layer, first column, columns <= 64, 0}
+hipError_t launch_styles_dlatents(const float* dlatents, const float* avg, const float* psi, const float* WT, const float* b,
+                                  const int4* tiles, int num_tiles, float* styles, int n, int K, int J, int NL, hipStream_t s);
 hipError_t launch_torgb(const float* x, const Aff* aff, const float* w, const float* b, float* rgb,
                         uint8_t* img, int n, int H, int W, int C, int nc, int bf16, hipStream_t s);
 hipError_t launch_export_nchw(const float* x, const Aff* aff, float* out, int n, int H, int W, int C, int bf16, hipStream_t s);

@@ -9,12 +9,19 @@ the WHOLE batch array (``:105,122``).  Additions: explicit latents/noise for rep
 ``keep_on_device`` to skip the 132.8 MB/sample host round trip of the reference
 (``:103-114``), and ``generate_batch`` -- the fused generator+decoder step used by
 ``main.py generate`` -- which never materialises the features.
+
+The two StyleGAN sampling controls: ``truncation_psi`` replaces the weight file's truncation vector (a float or
+2*(max_res_log2-1) floats); ``style_mix_prob > 0`` makes ``generate_indexed`` mix the styles of two latents per sample by the
+shard-invariant plan of ``style_mix``, through the per-layer (W-space) step ``gsa_generate_w``.  ``generate_batch_w`` runs that
+step on caller-made dlatents.  The W path runs eager: it is never captured into a hipGraph.  With the defaults every call runs
+the z path exactly as before.
 """
 import os
 
 import numpy as np
 import torch
 
+from . import style_mix as _style_mix
 from . import weights as _weights
 from ._runtime import current_stream_ptr, split_sizes, to_device_f32
 from .dataset_writer import STATUS_RING_DEPTH
@@ -26,7 +33,10 @@ _GRAPH_CAPTURES_MAX = 16
 
 
 class ImageGenerator:
-    def __init__(self, gpu_ids, gan_dir, gan="ffhq", batch_size=4, return_latents=False, seed=0, precision="fp32"):
+    style_mix_prob = 0.0
+
+    def __init__(self, gpu_ids, gan_dir, gan="ffhq", batch_size=4, return_latents=False, seed=0, precision="fp32",
+                 truncation_psi=None, style_mix_prob=0.0):
         max_res_log2_dict = _weights.GAN_MAX_RES_LOG2
         self.max_res_log2 = max_res_log2_dict[gan]
         self.latent_size = 512
@@ -38,6 +48,7 @@ class ImageGenerator:
                                "(the reference falls back to mx.cpu(), image_generator.py:17)")
         self.ctx = gpu_ids      # the reference's device list (image_generator.py:17): one weight replica per entry
         self.precision = precision
+        self.style_mix_prob = self._check_mix_prob(style_mix_prob)
         self.cfg = self._get_config(max_res_log2=self.max_res_log2)
         stylegan_name = "stylegan-%s.params" % gan
         from . import params as _params
@@ -45,7 +56,7 @@ class ImageGenerator:
         self._gens = []
         for dev in gpu_ids:
             g = self._get_G(self.cfg, dev)
-            g.load_parameters(tensors, ignore_extra=True)
+            g.load_parameters(tensors, ignore_extra=True, truncation_psi=truncation_psi)
             self._gens.append(g)
         self.netG = self._gens[0]
         self._decoder = None
@@ -57,7 +68,7 @@ class ImageGenerator:
 
     @classmethod
     def from_params(cls, gcfg, gparams, dcfg=None, dparams=None, gpu_ids=(0,), batch_size=4,
-                    return_latents=False, seed=0, precision="fp32"):
+                    return_latents=False, seed=0, precision="fp32", truncation_psi=None, style_mix_prob=0.0):
         """Build from in-memory weights (tests, benchmarks: no pretrained files exist here)."""
         self = cls.__new__(cls)
         self.max_res_log2 = gcfg["max_res_log2"]
@@ -67,10 +78,11 @@ class ImageGenerator:
         self.ctx = list(gpu_ids)
         self.cfg = dict(gcfg)
         self.precision = precision
+        self.style_mix_prob = cls._check_mix_prob(style_mix_prob)
         self._gens = []
         for dev in self.ctx:
             g = Generator(self.cfg, device=dev, precision=precision)
-            g.load_parameters(gparams)
+            g.load_parameters(gparams, truncation_psi=truncation_psi)
             self._gens.append(g)
         self.netG = self._gens[0]
         self._decoder = None
@@ -82,6 +94,13 @@ class ImageGenerator:
         for g in self._gens:
             g.seed(seed)
         return self
+
+    @staticmethod
+    def _check_mix_prob(p):
+        p = float(p)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("style_mix_prob must be in [0, 1], got %r" % p)
+        return p
 
     def _get_G(self, config, device):
         return Generator(config, device=device, precision=self.precision)
@@ -164,7 +183,10 @@ class ImageGenerator:
     # -- fused hot path ---------------------------------------------------------------------
     def generate_indexed(self, first_index, n, seed=0, out=None):
         """``generate_batch`` for the global samples ``first_index .. first_index+n-1`` with counter-based latents
-        and noise (``Generator.draw_indexed``): the dataset does not depend on how it is sharded."""
+        and noise (``Generator.draw_indexed``): the dataset does not depend on how it is sharded.  With ``style_mix_prob > 0``
+        the samples are style-mixed by the plan of ``style_mix`` (also a function of the global index) on the eager W path."""
+        if self.style_mix_prob > 0:
+            return self._generate_indexed_mixed(first_index, n, seed, out)
         if len(self._gens) == 1:
             z, noise = self.netG.draw_indexed(first_index, n, seed)
             return self.generate_batch(z, noise, out=out)
@@ -175,6 +197,30 @@ class ImageGenerator:
                 z, noise = g.draw_indexed(first_index + lo, hi - lo, seed)
                 parts.append(self._generate_on(r, z, noise))
         return self._collect(parts, n, out)
+
+    def _generate_indexed_mixed(self, first_index, n, seed, out):
+        if self._decoder is None:
+            raise RuntimeError("attach_decoder() first")
+        parts = []
+        for r, lo, hi in split_sizes(n, len(self._gens)):
+            g = self._gens[r]
+            with torch.cuda.device(g._model.device):
+                dl, noise = self._mixed_dlatents(g, first_index + lo, hi - lo, seed)
+                parts.append(self._generate_on_w(r, dl, noise, out if len(self._gens) == 1 else None))
+        if len(self._gens) == 1:
+            return parts[0]
+        return self._collect(parts, n, out)
+
+    def _mixed_dlatents(self, g, first_index, n, seed):
+        """(dlatents (n, L, latent), noise) of the global samples first_index.. on replica ``g``: layer l of a sample is
+        mapping(z) or, mixed and l >= cutoff, mapping(z_b) (``style_mix``); mapping runs once per latent set of n rows."""
+        z, noise = g.draw_indexed(first_index, n, seed)
+        z_b = g.draw_indexed_latents(first_index, n, _style_mix.mix_seed(seed))
+        L = g.num_style_layers
+        mix, cutoff = _style_mix.mix_plan(seed, first_index, n, self.style_mix_prob, L)
+        sel = torch.from_numpy(_style_mix.layer_select(mix, cutoff, L)).to(g._model.device)
+        w_a, w_b = g.mapping(z), g.mapping(z_b)
+        return torch.where(sel[:, :, None], w_b[:, None, :], w_a[:, None, :]).contiguous(), noise
 
     def _check_out(self, out, n, dev):
         R, nc = 2 ** self.max_res_log2, self.netG.nc
@@ -228,6 +274,21 @@ class ImageGenerator:
                 cache[key] = graph
                 return img, mask
         model.ctx.generate(current_stream_ptr(dev), n, z.data_ptr(), nptrs, img.data_ptr(), mask.data_ptr())
+        return img, mask
+
+    def _generate_on_w(self, r, dlatents, noise, out=None):
+        """The fused step from per-layer dlatents on replica ``r`` (gsa_generate_w); always eager."""
+        g = self._gens[r]
+        dl, noise, n = g._prepare_w(dlatents, noise)
+        dev = g._model.device
+        R = 2 ** self.max_res_log2
+        if out is None:
+            img = torch.empty((n, R, R, g.nc), device=dev, dtype=torch.uint8)
+            mask = torch.empty((n, R, R), device=dev, dtype=torch.uint8)
+        else:
+            img, mask = self._check_out(out, n, dev)
+        g._model.ctx.generate_w(current_stream_ptr(dev), n, dl.data_ptr(), g.num_style_layers, [a.data_ptr() for a in noise],
+                                img.data_ptr(), mask.data_ptr())
         return img, mask
 
     @staticmethod
@@ -337,4 +398,18 @@ class ImageGenerator:
         for r, lo, hi in split_sizes(n, len(self._gens)):
             with torch.cuda.device(self._gens[r]._model.device):
                 parts.append(self._generate_on(r, z[lo:hi], None if noise is None else [a[lo:hi] for a in noise]))
+        return self._collect(parts, n, out)
+
+    def generate_batch_w(self, dlatents, noise=None, out=None):
+        """``generate_batch`` from per-layer latents: dlatents (N, L, 512), untruncated (the loaded ``truncation_psi`` is
+        applied per layer), L = 2*(max_res_log2-1).  Split over the replicas like ``generate_batch``; eager (no hipGraph)."""
+        if self._decoder is None:
+            raise RuntimeError("attach_decoder() first")
+        if len(self._gens) == 1:
+            return self._generate_on_w(0, dlatents, noise, out)
+        n = len(dlatents)
+        parts = []
+        for r, lo, hi in split_sizes(n, len(self._gens)):
+            with torch.cuda.device(self._gens[r]._model.device):
+                parts.append(self._generate_on_w(r, dlatents[lo:hi], None if noise is None else [a[lo:hi] for a in noise]))
         return self._collect(parts, n, out)

@@ -65,13 +65,16 @@ def generate(cfg, limit=None, workers=None):
     batch = cfg["GAN_BATCH_SIZE_PER_GPU"] * len(gan_ids)      # reference main.py:87
     seed = int(cfg.get("SEED", 0))             # additive key: seed of the counter-based latents/noise
     precision = cfg.get("PRECISION", "fp32")   # additive key: "bf16" = bf16 MFMA operands (BASELINE config 5)
+    truncation_psi = cfg.get("TRUNCATION_PSI")                # additive key: replaces the weight file's truncation vector
+    style_mix_prob = float(cfg.get("STYLE_MIX_PROB", 0.0))    # additive key: share of style-mixed samples (style_mix.py)
 
     solver = SegSolver(GAN_MAX_RES_LOG2[gan], os.path.join(root_dir, "data"), os.path.join(root_dir, "checkpoints"),
                        gpu_ids=solver_ids, keep_weights=False, precision=precision)
     if not solver.is_trained:
         print("train Decoder first!")   # reference main.py:82-84
         return -1
-    netG = ImageGenerator(gpu_ids=gan_ids, gan_dir=gan_dir, gan=gan, batch_size=batch, precision=precision)
+    netG = ImageGenerator(gpu_ids=gan_ids, gan_dir=gan_dir, gan=gan, batch_size=batch, precision=precision,
+                          truncation_psi=truncation_psi, style_mix_prob=style_mix_prob)
     netG.attach_decoder(solver.cfg, solver.net)
     dst_dir = os.path.join(root_dir, "dataset", "train_generated")
     os.makedirs(dst_dir, exist_ok=True)
@@ -103,7 +106,8 @@ def export_for_annotation(cfg, count):
     from .image_generator import ImageGenerator
     gpu = list(cfg["GAN_GPU_IDS"])[0]
     netG = ImageGenerator(gpu_ids=[gpu], gan_dir=cfg["GAN_DIR"], gan=cfg["GAN"], batch_size=cfg["GAN_BATCH_SIZE_PER_GPU"],
-                          precision=cfg.get("PRECISION", "fp32"), seed=int(cfg.get("SEED", 0)))
+                          precision=cfg.get("PRECISION", "fp32"), seed=int(cfg.get("SEED", 0)),
+                          truncation_psi=cfg.get("TRUNCATION_PSI"))     # annotation samples are never style-mixed
     dst = os.path.join(cfg["BASE_DIR"], "data")
     for i, (img, feats) in enumerate(netG.get_images(count)):
         annotation_io.export_sample(dst, i, img, feats)

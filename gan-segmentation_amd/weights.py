@@ -57,6 +57,25 @@ def num_style_layers(cfg):
     return 2 * (cfg["max_res_log2"] - 1)
 
 
+def with_truncation_psi(tensors, psi, num_layers):
+    """``tensors`` with its ``truncation_psi`` vector replaced by ``psi`` (the override of ``ImageGenerator(truncation_psi=...)``):
+    a float (every layer) or a sequence of ``num_layers`` floats, layer l = 0 .. 2*(max_res_log2-1)-1.  ``None`` returns
+    ``tensors`` itself.  A new dict otherwise (the caller's is not modified); a wrong length or a non-finite value raises
+    ValueError."""
+    if psi is None:
+        return tensors
+    a = np.asarray(psi, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full(num_layers, float(a))
+    if a.ndim != 1 or a.shape[0] != num_layers:
+        raise ValueError("truncation_psi must be a float or a sequence of %d floats, got shape %s" % (num_layers, a.shape))
+    if not np.all(np.isfinite(a)):
+        raise ValueError("truncation_psi must be finite: %s" % a)
+    out = dict(tensors)
+    out["truncation_psi"] = a.astype(np.float32)
+    return out
+
+
 def decoder_config(max_res_log2=10, num_classes=2, in_channels=None):
     """Inference-relevant part of reference seg_solver.py:83-132."""
     features = [32, 32, 32, 32, 32, 32, 32, 32, 16][:max_res_log2 - 1] + [num_classes]

@@ -30,7 +30,7 @@
  *  - tensors crossing the boundary use the reference's layouts: fp32 NCHW activations,
  *    OIHW conv weights, (N,H,W,3) u8 RGB images, (N,H,W) u8 masks.
  *
- * The same signatures with the prefix `gsao_` are exported by the CPU oracle
+ * The same signatures with the prefix `gsao_` (the W-space entries excepted) are exported by the CPU oracle
  * (oracle/c/gsa_oracle.c, test infrastructure only) with every pointer a host pointer.
  */
 #ifndef GSA_H
@@ -138,6 +138,26 @@ int gsa_decoder_forward(gsa_ctx* ctx, void* stream, int32_t n, const float* cons
  * gsa_generator_forward + gsa_decoder_forward on the same inputs. */
 int gsa_generate(gsa_ctx* ctx, void* stream, int32_t n, const float* z,
                  const float* const* noise, int32_t num_noise, uint8_t* img, uint8_t* mask);
+
+/* --- W space (StyleGAN's mapping output and per-layer synthesis input) ------------------------------------------------
+ * Layer l runs over 0 .. 2*(max_res_log2-1)-1, the order of `truncation_psi` and of the noise planes; level lv uses layers 2lv
+ * and 2lv+1.  The committed truncation_psi is applied per layer (x = latent_avg*(1-psi_l) + w*psi_l), as in the z path. */
+
+/* The mapping network alone (reference networks_stylegan.py:128-139): z dev (N, latent_size) -> w dev (N, latent_size), the
+ * UNtruncated mapping output.  The same launch as the forward's first step; its time-out word is reported by gsa_check /
+ * gsa_status_snapshot like the step's.  n <= the reserved batch (GSA_ERR_STATE otherwise). */
+int gsa_mapping_forward(gsa_ctx* ctx, void* stream, int32_t n, const float* z, float* w);
+
+/* gsa_generator_forward with per-layer latents instead of z: dlatents dev (N, num_layers, latent_size) fp32, untruncated;
+ * style layer l reads row l.  num_layers must be 2*(max_res_log2-1) and dlatents non-null (GSA_ERR_INVALID otherwise).  With
+ * every row of a sample equal to gsa_mapping_forward's w the outputs are bitwise those of gsa_generator_forward on its z. */
+int gsa_generator_forward_w(gsa_ctx* ctx, void* stream, int32_t n, const float* dlatents, int32_t num_layers,
+                            const float* const* noise, int32_t num_noise, float* rgb, uint8_t* img,
+                            float* const* feats, int32_t num_feats);
+
+/* gsa_generate with per-layer latents: bitwise identical to gsa_generator_forward_w + gsa_decoder_forward. */
+int gsa_generate_w(gsa_ctx* ctx, void* stream, int32_t n, const float* dlatents, int32_t num_layers,
+                   const float* const* noise, int32_t num_noise, uint8_t* img, uint8_t* mask);
 
 /* gsa_generate runs the decoder on a second HIP stream beside the synthesis of the higher
  * resolutions (fork/join through events).  `levels` = number of decoder levels placed there; negative = the default:
