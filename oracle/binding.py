@@ -60,6 +60,9 @@ def api():
             "gsao_generator_forward": (c.c_int, [vp, vp, i32, vp, pp, i32, vp, vp, pp, i32]),
             "gsao_decoder_forward": (c.c_int, [vp, vp, i32, pp, i32, vp, vp]),
             "gsao_generate": (c.c_int, [vp, vp, i32, vp, pp, i32, vp, vp]),
+            "gsao_mapping_forward": (c.c_int, [vp, vp, i32, vp, vp]),
+            "gsao_generator_forward_w": (c.c_int, [vp, vp, i32, vp, i32, pp, i32, vp, vp, pp, i32]),
+            "gsao_generate_w": (c.c_int, [vp, vp, i32, vp, i32, pp, i32, vp, vp]),
             "gsao_version": (c.c_char_p, []),
         }
         for name, (res, args) in sig.items():
@@ -163,4 +166,50 @@ class Oracle:
         mask = np.empty((n, R, R), np.uint8)
         self._check(self.lib.gsao_generate(self._h, None, n, z.ctypes.data, _ptrs(noise), len(noise), img.ctypes.data, mask.ctypes.data),
                     "generate")
+        return img, mask
+
+    # -- W space (include/gsa.h gsa_mapping_forward / gsa_generator_forward_w / gsa_generate_w) --------------------------
+
+    def mapping(self, z):
+        """-> w (N, latent) f32: the untruncated mapping output of z (N, latent)."""
+        z = np.ascontiguousarray(z, np.float32)
+        if z.ndim != 2 or z.shape[1] != self.gcfg["latent_size"]:
+            raise OracleError("z must have shape (N, %d), got %s" % (self.gcfg["latent_size"], z.shape))
+        w = np.empty_like(z)
+        self._check(self.lib.gsao_mapping_forward(self._h, None, z.shape[0], z.ctypes.data, w.ctypes.data), "mapping_forward")
+        return w
+
+    def _dlatents(self, dlatents):
+        """dlatents (N, num_layers, latent) as contiguous f32; num_layers is passed on as given, for the library to check."""
+        dl = np.ascontiguousarray(dlatents, np.float32)
+        if dl.ndim != 3 or dl.shape[2] != self.gcfg["latent_size"]:
+            raise OracleError("dlatents must have shape (N, num_layers, %d), got %s" % (self.gcfg["latent_size"], dl.shape))
+        return dl
+
+    def generator_w(self, dlatents, noise, want_feats=True):
+        """generator() from per-layer latents (N, L, latent), untruncated: style layer l reads row l.
+        -> (rgb (N,3,R,R) f32, img (N,R,R,3) u8, [feats NCHW])"""
+        dl = self._dlatents(dlatents)
+        noise = [np.ascontiguousarray(a, np.float32) for a in noise]
+        n = dl.shape[0]
+        shapes = self._gen_shapes(n)
+        R, nc = shapes[-1][2], self.gcfg["channels"]
+        rgb = np.empty((n, nc, R, R), np.float32)
+        img = np.empty((n, R, R, nc), np.uint8)
+        feats = [np.empty(s, np.float32) for s in shapes] if want_feats else None
+        self._check(self.lib.gsao_generator_forward_w(self._h, None, n, dl.ctypes.data, dl.shape[1], _ptrs(noise), len(noise),
+                                                      rgb.ctypes.data, img.ctypes.data, _ptrs(feats) if want_feats else None,
+                                                      len(feats) if want_feats else 0), "generator_forward_w")
+        return rgb, img, feats
+
+    def generate_w(self, dlatents, noise):
+        """generate() from per-layer latents (N, L, latent). -> (img (N,R,R,3) u8, mask (N,R,R) u8)"""
+        dl = self._dlatents(dlatents)
+        noise = [np.ascontiguousarray(a, np.float32) for a in noise]
+        n = dl.shape[0]
+        R, nc = 2 ** self.gcfg["max_res_log2"], self.gcfg["channels"]
+        img = np.empty((n, R, R, nc), np.uint8)
+        mask = np.empty((n, R, R), np.uint8)
+        self._check(self.lib.gsao_generate_w(self._h, None, n, dl.ctypes.data, dl.shape[1], _ptrs(noise), len(noise),
+                                             img.ctypes.data, mask.ctypes.data), "generate_w")
         return img, mask

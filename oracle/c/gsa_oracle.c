@@ -14,6 +14,7 @@
  * What is restated (reference file:line):
  *   mapping, PixelNorm, DenseW ........ networks_stylegan.py:128-139, 479-524, 558-565
  *   truncation lerp ................... networks_stylegan.py:158-163, 170-189
+ *   W space (per-layer latents) ....... include/gsa.h gsa_mapping_forward / gsa_generator_forward_w / gsa_generate_w
  *   StyleGeneratorBlock ............... networks_stylegan.py:6-73
  *   Conv2DW / Conv2DTransposeW ........ networks_stylegan.py:354-476 (weight*std*lr_mult :407-412)
  *   Blur .............................. networks_stylegan.py:200-236
@@ -1017,11 +1018,24 @@ static void nchw_to_nhwc(const float* in, int H, int W, int C, float* out) {
 
 GSAO_API int gsao_reserve(gsao_ctx* c, int32_t max_batch) { (void)c; (void)max_batch; return GSA_OK; }
 
-GSAO_API int gsao_generator_forward(gsao_ctx* c, void* stream, int32_t n, const float* z, const float* const* noise,
-                                    int32_t num_noise, float* rgb, uint8_t* img, float* const* feats, int32_t num_feats) {
-    (void)stream;
-    if (!c || !c->g_ready) return fail(c, GSA_ERR_STATE, "generator_commit first%s (%ld)", "", 0);
-    if (n < 0 || !z || !noise) return fail(c, GSA_ERR_INVALID, "bad arguments to generator_forward%s (%ld)", "", n);
+/* mapping of one sample, reference :128-139, :558-565: PixelNorm then 8 x (dense, lrelu); w2 is scratch of L floats */
+static void mapping_one(const gsao_ctx* c, const float* zs, float* w, float* w2) {
+    const int L = c->gc.latent_size;
+    float ss = 0.0f;
+    for (int k = 0; k < L; ++k) ss = fmaf(zs[k], zs[k], ss);
+    float rn = 1.0f / sqrtf(ss / (float)L + 1e-8f);
+    for (int k = 0; k < L; ++k) w[k] = zs[k] * rn;
+    for (int i = 0; i < 8; ++i) {
+        dense(w, c->map_w[i], c->map_b[i], L, L, w2);
+        for (int k = 0; k < L; ++k) w[k] = lrelu(w2[k]);
+    }
+}
+
+/* The synthesis of n samples from either z (N, L), whose mapped w every style layer reads, or dlatents (N, 2*nlev, L), whose
+ * row l style layer l reads (exactly one of z / dlat is non-null).  Everything after the latent row is the same code. */
+static int synthesis(gsao_ctx* c, int32_t n, const float* z, const float* dlat, const float* const* noise,
+                     int32_t num_noise, float* rgb, uint8_t* img, float* const* feats, int32_t num_feats) {
+    if (n < 0 || (!z && !dlat) || !noise) return fail(c, GSA_ERR_INVALID, "bad arguments to generator_forward%s (%ld)", "", n);
     if (num_noise != 2 * c->nlev || (feats && num_feats != c->nlev))
         return fail(c, GSA_ERR_INVALID, "noise / feature pointer counts do not match this generator%s (%ld)", "", num_noise);
     const int L = c->gc.latent_size, nlev = c->nlev, nc = c->gc.channels;
@@ -1047,15 +1061,13 @@ GSAO_API int gsao_generator_forward(gsao_ctx* c, void* stream, int32_t n, const 
     if (!xa || !xb || !xc || !w || !w2 || !dl || !style || !I1 || !I2 || !aff) return fail(c, GSA_ERR_NOMEM, "out of memory in generator_forward%s (%ld)", "", 0);
 
     for (int s = 0; s < n; ++s) {
-        /* mapping: PixelNorm then 8 x (dense, lrelu) -- reference :128-139, :558-565 */
-        const float* zs = z + (size_t)s * L;
-        float ss = 0.0f;
-        for (int k = 0; k < L; ++k) ss = fmaf(zs[k], zs[k], ss);
-        float rn = 1.0f / sqrtf(ss / (float)L + 1e-8f);
-        for (int k = 0; k < L; ++k) w[k] = zs[k] * rn;
-        for (int i = 0; i < 8; ++i) {
-            dense(w, c->map_w[i], c->map_b[i], L, L, w2);
-            for (int k = 0; k < L; ++k) w[k] = lrelu(w2[k]);
+        const float* rows;              /* the latent of style layer li is rows + li * row_step */
+        size_t row_step;
+        if (z) {
+            mapping_one(c, z + (size_t)s * L, w, w2);
+            rows = w, row_step = 0;
+        } else {
+            rows = dlat + (size_t)s * 2 * nlev * L, row_step = (size_t)L;
         }
         for (int l = 0; l < nlev; ++l) {
             const gen_block* B = &c->blk[l];
@@ -1066,7 +1078,8 @@ GSAO_API int gsao_generator_forward(gsao_ctx* c, void* stream, int32_t n, const 
                 const float* nz = noise[li] + (size_t)s * npix;
                 /* truncation lerp, reference :158-163 */
                 const float psi = c->psi[li], om = 1.0f - psi;
-                for (int q = 0; q < L; ++q) dl[q] = c->latent_avg[q] * om + w[q] * psi;
+                const float* wl = rows + li * row_step;
+                for (int q = 0; q < L; ++q) dl[q] = c->latent_avg[q] * om + wl[q] * psi;
                 dense(dl, B->aff_w[k], B->aff_b[k], 2 * C, L, style);
                 if (k == 0) {
                     if (!B->has_conv1) {
@@ -1114,6 +1127,45 @@ GSAO_API int gsao_generator_forward(gsao_ctx* c, void* stream, int32_t n, const 
     }
     free(xa); free(xb); free(xc); free(w); free(w2); free(dl); free(style); free(I1); free(I2); free(aff);
     return GSA_OK;
+}
+
+GSAO_API int gsao_generator_forward(gsao_ctx* c, void* stream, int32_t n, const float* z, const float* const* noise,
+                                    int32_t num_noise, float* rgb, uint8_t* img, float* const* feats, int32_t num_feats) {
+    (void)stream;
+    if (!c || !c->g_ready) return fail(c, GSA_ERR_STATE, "generator_commit first%s (%ld)", "", 0);
+    return synthesis(c, n, z, NULL, noise, num_noise, rgb, img, feats, num_feats);
+}
+
+/* ---------------------------------------------------------------- W space (include/gsa.h) */
+
+/* z (N, L) -> w (N, L): the untruncated mapping output, as the z path computes it */
+GSAO_API int gsao_mapping_forward(gsao_ctx* c, void* stream, int32_t n, const float* z, float* w) {
+    (void)stream;
+    if (!c || !c->g_ready) return fail(c, GSA_ERR_STATE, "generator_commit first%s (%ld)", "", 0);
+    if (n < 0 || !z || !w) return fail(c, GSA_ERR_INVALID, "bad arguments to mapping_forward: null z or w%s (%ld)", "", n);
+    const int L = c->gc.latent_size;
+    float* w2 = (float*)malloc(sizeof(float) * L);
+    if (!w2) return fail(c, GSA_ERR_NOMEM, "out of memory in mapping_forward%s (%ld)", "", 0);
+    for (int s = 0; s < n; ++s) mapping_one(c, z + (size_t)s * L, w + (size_t)s * L, w2);
+    free(w2);
+    return GSA_OK;
+}
+
+static int check_dlatents(gsao_ctx* c, const float* dlat, int32_t num_layers) {
+    if (!dlat) return fail(c, GSA_ERR_INVALID, "dlatents is null%s (%ld)", "", 0);
+    if (num_layers != 2 * c->nlev)
+        return fail(c, GSA_ERR_INVALID, "dlatents must have 2*(max_res_log2-1) layers%s, got %ld", "", num_layers);
+    return GSA_OK;
+}
+
+GSAO_API int gsao_generator_forward_w(gsao_ctx* c, void* stream, int32_t n, const float* dlatents, int32_t num_layers,
+                                      const float* const* noise, int32_t num_noise, float* rgb, uint8_t* img,
+                                      float* const* feats, int32_t num_feats) {
+    (void)stream;
+    if (!c || !c->g_ready) return fail(c, GSA_ERR_STATE, "generator_commit first%s (%ld)", "", 0);
+    int rc = check_dlatents(c, dlatents, num_layers);
+    if (rc != GSA_OK) return rc;
+    return synthesis(c, n, NULL, dlatents, noise, num_noise, rgb, img, feats, num_feats);
 }
 
 /* ---------------------------------------------------------------- decoder */
@@ -1323,8 +1375,9 @@ GSAO_API int gsao_decoder_forward(gsao_ctx* c, void* stream, int32_t n, const fl
     return GSA_OK;
 }
 
-GSAO_API int gsao_generate(gsao_ctx* c, void* stream, int32_t n, const float* z, const float* const* noise, int32_t num_noise,
-                           uint8_t* img, uint8_t* mask) {
+/* generator then decoder, one sample at a time; the latents are z (N, L) or dlatents (N, 2*nlev, L), as in synthesis() */
+static int generate(gsao_ctx* c, int32_t n, const float* z, const float* dlat, const float* const* noise, int32_t num_noise,
+                    uint8_t* img, uint8_t* mask) {
     if (!c || !c->g_ready || !c->d_ready) return fail(c, GSA_ERR_STATE, "commit generator and decoder first%s (%ld)", "", 0);
     const int nlev = c->nlev;
     if (num_noise != 2 * nlev) return fail(c, GSA_ERR_INVALID, "noise plane count does not match this generator%s (%ld)", "", num_noise);
@@ -1343,10 +1396,26 @@ GSAO_API int gsao_generate(gsao_ctx* c, void* stream, int32_t n, const float* z,
             nz[2 * l + 1] = noise[2 * l + 1] + (size_t)s * npix;
         }
         const size_t R = (size_t)1 << c->gc.max_res_log2;
-        rc = gsao_generator_forward(c, stream, 1, z + (size_t)s * c->gc.latent_size, nz, 2 * nlev, NULL,
-                                    img ? img + (size_t)s * R * R * c->gc.channels : NULL, feats, nlev);
-        if (rc == GSA_OK) rc = gsao_decoder_forward(c, stream, 1, cf, nlev, NULL, mask ? mask + (size_t)s * R * R : NULL);
+        const size_t L = (size_t)c->gc.latent_size;
+        rc = synthesis(c, 1, z ? z + (size_t)s * L : NULL, dlat ? dlat + (size_t)s * 2 * nlev * L : NULL, nz, 2 * nlev, NULL,
+                       img ? img + (size_t)s * R * R * c->gc.channels : NULL, feats, nlev);
+        if (rc == GSA_OK) rc = gsao_decoder_forward(c, NULL, 1, cf, nlev, NULL, mask ? mask + (size_t)s * R * R : NULL);
         for (int l = 0; l < nlev; ++l) free(feats[l]);
     }
     return rc;
+}
+
+GSAO_API int gsao_generate(gsao_ctx* c, void* stream, int32_t n, const float* z, const float* const* noise, int32_t num_noise,
+                           uint8_t* img, uint8_t* mask) {
+    (void)stream;
+    return generate(c, n, z, NULL, noise, num_noise, img, mask);
+}
+
+GSAO_API int gsao_generate_w(gsao_ctx* c, void* stream, int32_t n, const float* dlatents, int32_t num_layers,
+                             const float* const* noise, int32_t num_noise, uint8_t* img, uint8_t* mask) {
+    (void)stream;
+    if (!c || !c->g_ready || !c->d_ready) return fail(c, GSA_ERR_STATE, "commit generator and decoder first%s (%ld)", "", 0);
+    int rc = check_dlatents(c, dlatents, num_layers);
+    if (rc != GSA_OK) return rc;
+    return generate(c, n, NULL, dlatents, noise, num_noise, img, mask);
 }

@@ -108,23 +108,30 @@ class SemanticGenerator:
         y = self.adain(y, w2, "%d_adain_2" % R)
         return y
 
-    def __call__(self, z, noise):
+    def synthesis(self, dlatents, noise):
+        """The blocks and toRGB from per-layer latents (B, 2*(max_res_log2-1), latent), untruncated: style layer l (the order of
+        truncation_psi and of the noise planes; level r-2 uses layers 2(r-2) and 2(r-2)+1) reads row l, truncated by psi[l]."""
         cfg = self.cfg
-        z = _t(z, self.dtype)
+        dl = _t(dlatents, self.dtype)
         noise = [_t(n, self.dtype) for n in noise]
-        B = z.shape[0]
-        w = self.mapping(z)
+        B = dl.shape[0]
+        assert dl.dim() == 3 and dl.shape[1] == 2 * (cfg["max_res_log2"] - 1), tuple(dl.shape)
         psi = self.p["truncation_psi"]
         y = self.p["constant_tensor"].to(self.dtype).expand(B, -1, -1, -1)
         feats = []
         for r in range(2, cfg["max_res_log2"] + 1):
             l = 2 * (r - 2)
-            w1, w2 = self.lerp(psi[l], w), self.lerp(psi[l + 1], w)
+            w1, w2 = self.lerp(psi[l], dl[:, l]), self.lerp(psi[l + 1], dl[:, l + 1])
             y = self.block(r, y, w1, w2, noise[l], noise[l + 1])
             feats.append(y)
         R = 2 ** cfg["max_res_log2"]
         rgb = F.conv2d(y, self._w("%d_conv_to_rgb" % R), self._b("%d_conv_to_rgb" % R))
         return rgb, feats
+
+    def __call__(self, z, noise):
+        w = self.mapping(_t(z, self.dtype))
+        L = 2 * (self.cfg["max_res_log2"] - 1)
+        return self.synthesis(w[:, None, :].expand(-1, L, -1), noise)
 
 
 def transform_gan_back(rgb, imrange=(-1, 1)):
@@ -184,6 +191,14 @@ def predict_mask(logits):
     """reference seg_solver.py:326-327: argmax over classes (first max wins), (N,H,W,1) float32."""
     m = torch.argmax(logits, dim=1, keepdim=True)
     return m.permute(0, 2, 3, 1).to(torch.float32).numpy()
+
+
+def synthesis(gcfg, gparams, dcfg, dparams, dlatents, noise, dtype=torch.float32):
+    """The hot path from per-layer latents (B, L, latent): (rgb f32 NCHW, feats, logits), numpy."""
+    with torch.no_grad():
+        rgb, feats = SemanticGenerator(gcfg, gparams, dtype).synthesis(dlatents, noise)
+        logits = SemanticDecoder(dcfg, dparams, dtype)(*feats)
+    return rgb.numpy(), [f.numpy() for f in feats], logits.numpy()
 
 
 def generate(gcfg, gparams, dcfg, dparams, z, noise, dtype=torch.float32):

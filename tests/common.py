@@ -4,23 +4,56 @@ import numpy as np
 from gan_segmentation_amd import weights as W
 
 
-def reduced_setup(max_res_log2=7, batch=2, trivial_norm=False, seed=2):
+def lively(gp):
+    """The synthetic weights with the mapping layers scaled by 1/lr_mult (100), as trained StyleGAN files hold them: drawn at
+    unit scale, the eight lr_mult-0.01 layers shrink z away and w comes out the same to the last bit for every z."""
+    out = dict(gp)
+    for i in range(8):
+        out["mp_dense_%d_weight" % i] = gp["mp_dense_%d_weight" % i] * 100.0
+    return out
+
+
+def reduced_setup(max_res_log2=7, batch=2, trivial_norm=False, seed=2, live_mapping=False):
+    """live_mapping=True: the mapping layers of lively(), so that w depends on z."""
     gcfg = W.reduced_generator_config(max_res_log2)
     gp = W.synthetic_generator_params(gcfg, seed=seed, trivial_norm=trivial_norm)
+    if live_mapping:
+        gp = lively(gp)
     dcfg = W.decoder_config(max_res_log2, in_channels=W.generator_channels(gcfg))
     dp = W.synthetic_decoder_params(dcfg, seed=seed + 1)
     z, noise = W.synthetic_inputs(gcfg, batch)
     return gcfg, gp, dcfg, dp, z, noise
 
 
-def gan_setup(gan="ffhq", batch=1):
+def gan_setup(gan="ffhq", batch=1, live_mapping=False):
     mr = W.GAN_MAX_RES_LOG2[gan]
     gcfg = W.generator_config(mr)
     gp = W.synthetic_generator_params(gcfg, seed=2)
+    if live_mapping:
+        gp = lively(gp)
     dcfg = W.decoder_config(mr)
     dp = W.synthetic_decoder_params(dcfg, seed=3)
     z, noise = W.synthetic_inputs(gcfg, batch)
     return gcfg, gp, dcfg, dp, z, noise
+
+
+def odd_setup(batch, live_mapping=False):
+    """128 px with 48-channel levels: 96 style columns per layer (one 64-wide tile + one 32-wide) and odd decoder widths."""
+    gcfg = W.generator_config(max_res_log2=7, fmap_base=3072, fmap_max=48)
+    dcfg = W.decoder_config(7, in_channels=W.generator_channels(gcfg))
+    dcfg["features"] = [48, 32, 48, 80, 16, 48, 2]
+    gp = W.synthetic_generator_params(gcfg, seed=11, trivial_norm=False)
+    if live_mapping:
+        gp = lively(gp)
+    dp = W.synthetic_decoder_params(dcfg, seed=12)
+    z, noise = W.synthetic_inputs(gcfg, batch)
+    return gcfg, gp, dcfg, dp, z, noise
+
+
+def w_spread(w):
+    """max |w_i - w_0| over the samples of w (N, latent): how much the mapping output depends on z."""
+    w = np.asarray(w, np.float64)
+    return float(np.abs(w - w[:1]).max())
 
 
 def bench_setup(gan="ffhq", batch=8, rank=0):

@@ -5,7 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests.common import gan_setup, reduced_setup
+from tests.common import gan_setup, lively, odd_setup, reduced_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -16,34 +16,14 @@ def _same(a, b, what):
     assert np.array_equal(a, b), "%s: %d of %d values differ" % (what, int((a != b).sum()), a.size)
 
 
-def _lively(gp):
-    """The synthetic weights with the mapping layers scaled by 1/lr_mult (100), as trained StyleGAN files hold them: drawn at
-    unit scale, the eight lr_mult-0.01 layers shrink z away and w comes out the same to the last bit for every z."""
-    out = dict(gp)
-    for i in range(8):
-        out["mp_dense_%d_weight" % i] = gp["mp_dense_%d_weight" % i] * 100.0
-    return out
-
-
-def _odd_setup(batch):
-    from gan_segmentation_amd import weights as W
-    gcfg = W.generator_config(max_res_log2=7, fmap_base=3072, fmap_max=48)     # 96 style columns per layer: one 64-wide tile + 32
-    dcfg = W.decoder_config(7, in_channels=W.generator_channels(gcfg))
-    dcfg["features"] = [48, 32, 48, 80, 16, 48, 2]
-    gp = W.synthetic_generator_params(gcfg, seed=11, trivial_norm=False)
-    dp = W.synthetic_decoder_params(dcfg, seed=12)
-    z, noise = W.synthetic_inputs(gcfg, batch)
-    return gcfg, gp, dcfg, dp, z, noise
-
-
 def _setup(kind, batch):
     if kind == "reduced":
         gcfg, gp, dcfg, dp, z, noise = reduced_setup(7, batch=batch)
     elif kind == "odd":
-        gcfg, gp, dcfg, dp, z, noise = _odd_setup(batch)
+        gcfg, gp, dcfg, dp, z, noise = odd_setup(batch)
     else:
         gcfg, gp, dcfg, dp, z, noise = gan_setup("ffhq", batch)
-    return gcfg, _lively(gp), dcfg, dp, z, noise
+    return gcfg, lively(gp), dcfg, dp, z, noise
 
 
 def _build(gcfg, gp, dcfg, dp, batch, **kw):
@@ -103,32 +83,23 @@ def test_fused_w_step_equals_two_calls(torch_cuda):
 def _semantic_mixed(gcfg, gp, dcfg, dp, z_a, z_b, cutoffs, noise):
     """Torch composition of the reference-order restatement: per-sample layer routing of mapping(z_a) / mapping(z_b)."""
     import torch
+    from gan_segmentation_amd import style_mix as M
     from oracle import ref_semantic as S
-    G = S.SemanticGenerator(gcfg, gp)
     with torch.no_grad():
-        w_a, w_b = G.mapping(torch.from_numpy(z_a)), G.mapping(torch.from_numpy(z_b))
-        psi = G.p["truncation_psi"]
-        nz = [torch.from_numpy(np.asarray(a, dtype=np.float32)) for a in noise]
-        n = z_a.shape[0]
-        y = G.p["constant_tensor"].expand(n, -1, -1, -1)
-        cut = torch.as_tensor(cutoffs).reshape(-1, 1)
-        feats = []
-        for r in range(2, gcfg["max_res_log2"] + 1):
-            l = 2 * (r - 2)
-            ws = [torch.where(cut > k, w_a, w_b) for k in (l, l + 1)]
-            y = G.block(r, y, G.lerp(psi[l], ws[0]), G.lerp(psi[l + 1], ws[1]), nz[l], nz[l + 1])
-            feats.append(y)
-        R = 2 ** gcfg["max_res_log2"]
-        rgb = torch.nn.functional.conv2d(y, G._w("%d_conv_to_rgb" % R), G._b("%d_conv_to_rgb" % R))
-        logits = S.SemanticDecoder(dcfg, dp)(*feats)
-    return rgb.numpy(), logits.numpy()
+        G = S.SemanticGenerator(gcfg, gp)
+        w_a, w_b = G.mapping(torch.from_numpy(z_a)).numpy(), G.mapping(torch.from_numpy(z_b)).numpy()
+    L = 2 * (gcfg["max_res_log2"] - 1)
+    sel = M.layer_select(np.ones(len(cutoffs), bool), np.asarray(cutoffs), L)
+    dl = np.where(sel[:, :, None], w_b[:, None, :], w_a[:, None, :])
+    rgb, _feats, logits = S.synthesis(gcfg, gp, dcfg, dp, dl, noise)
+    return rgb, logits
 
 
 @pytest.mark.parametrize("kind,cutoffs", [("reduced", [1, 2, 3, 11]), ("ffhq", [8, 8])])
 def test_style_routing(torch_cuda, kind, cutoffs):
     """Mixed dlatents with the given cutoffs: the features of the levels fed only by layers < cutoff are those of the pure
-    z_a run bit for bit, a later level differs, and rgb / logits are within 1e-3 of the torch composition of the
-    reference-order restatement (the bar of test_semantic_tolerance)."""
+    z_a run bit for bit, a later level differs, rgb / logits are within 1e-3 of the torch composition of the
+    reference-order restatement (the bar of test_semantic_tolerance), and rgb / features / logits equal Oracle.generator_w."""
     import torch
     n = len(cutoffs)
     gcfg, gp, dcfg, dp, z, noise = _setup(kind, n)
@@ -150,6 +121,16 @@ def test_style_routing(torch_cuda, kind, cutoffs):
     srgb, slog = _semantic_mixed(gcfg, gp, dcfg, dp, np.asarray(z, np.float32), z_b, cutoffs, noise)
     assert np.abs(rgb.cpu().numpy() - srgb).max() <= 1e-3
     assert np.abs(logits.cpu().numpy() - slog).max() <= 1e-3
+    # and bit for bit the C oracle on the same dlatents (full size: the first sample only, to bound the oracle's time)
+    from oracle.binding import Oracle
+    o = Oracle(gcfg, gp, dcfg, dp)
+    k = n if kind == "reduced" else 1
+    rgb_o, _img_o, feats_o = o.generator_w(dl[:k].cpu().numpy(), [np.asarray(a)[:k] for a in noise])
+    logits_o, _mask_o = o.decoder(feats_o)
+    _same(rgb.cpu().numpy()[:k], rgb_o, "rgb vs the oracle")
+    for lv, f in enumerate(feats_o):
+        _same(feats[lv].cpu().numpy()[:k], f, "feature %d vs the oracle" % lv)
+    _same(logits.cpu().numpy()[:k], logits_o, "logits vs the oracle")
 
 
 @pytest.mark.parametrize("psi", [0.5, "per-layer"])
@@ -243,7 +224,7 @@ def _cli_dirs(tmp_path, name):
     gan_dir, base = root / "stylegan-models", root / "exp"
     gan_dir.mkdir(parents=True)
     (base / "checkpoints").mkdir(parents=True)
-    gp, dp = _lively(W.synthetic_generator_params(gcfg)), W.synthetic_decoder_params(dcfg)
+    gp, dp = lively(W.synthetic_generator_params(gcfg)), W.synthetic_decoder_params(dcfg)
     P.save_params(str(gan_dir / "stylegan-bedrooms.params"), W.generator_names_to_scheme_s(gp))
     P.save_params(str(base / "checkpoints" / "checkpoint_last.params"), dp)
     cfg = {"BASE_DIR": str(base), "GAN": "bedrooms", "GAN_DIR": str(gan_dir), "GAN_GPU_IDS": [0],
