@@ -24,7 +24,7 @@ API_SYMBOLS = (
     "generator_forward", "decoder_forward", "generate", "set_overlap", "set_precision", "segmentation_eval", "fill_inputs",
     "profile_enable", "profile_collect",
     "profile_entry", "profile_reset", "version", "check", "status_snapshot", "debug_inject",
-    "mapping_forward", "generator_forward_w", "generate_w",
+    "mapping_forward", "generator_forward_w", "generate_w", "generate_downscaled",
 )
 
 
@@ -81,6 +81,7 @@ class Api:
             "mapping_forward": (c.c_int, [vp, vp, i32, vp, vp]),
             "generator_forward_w": (c.c_int, [vp, vp, i32, vp, i32, c.POINTER(vp), i32, vp, vp, c.POINTER(vp), i32]),
             "generate_w": (c.c_int, [vp, vp, i32, vp, i32, c.POINTER(vp), i32, vp, vp]),
+            "generate_downscaled": (c.c_int, [vp, vp, i32, vp, vp, i32, c.POINTER(vp), i32, i32, vp, vp]),
             "set_overlap": (c.c_int, [vp, i32]),
             "set_precision": (c.c_int, [vp, i32]),
             "segmentation_eval": (c.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
@@ -269,6 +270,12 @@ class Context:
         """gsa_generate_w: the fused step from per-layer dlatents."""
         self._check(self.api.generate_w(self._h, stream, n, dlatents, num_layers, _ptr_array(noise), len(noise), img, mask),
                     "generate_w")
+        self._after_step()
+
+    def generate_downscaled(self, stream, n, z, dlatents, num_layers, noise, factor, img, mask):
+        """gsa_generate_downscaled: the fused step from z or (z None) per-layer dlatents, the pair at 1/factor resolution."""
+        self._check(self.api.generate_downscaled(self._h, stream, n, z, dlatents, num_layers, _ptr_array(noise), len(noise), int(factor),
+                                                 img, mask), "generate_downscaled")
         self._after_step()
 
     def set_precision(self, precision):

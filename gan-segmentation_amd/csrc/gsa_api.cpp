@@ -1217,8 +1217,10 @@ static ConvParams cvt_params(gsa_ctx* c, int i, const float* src, const Aff* aff
 
 // feats_nhwc[i] / feat_aff[i]: decoder inputs in kernel layout (aff may be null).  rgb_img (gsa_generate only, the caller checked
 // wino_lean_fuses_torgb): the LAST level's cvt convolution also writes toRGB's uint8 image -- it stages the very tensor toRGB reads.
+// factor > 1 (gsa_generate_downscaled): the last level's final conv writes the mask at 1/factor resolution and no logits.
 static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsrc, const Aff* const* faff, float* logits,
-                       uint8_t* mask, int i_begin = 0, int i_end = -1, bool wait_levels = false, uint8_t* rgb_img = nullptr) {
+                       uint8_t* mask, int i_begin = 0, int i_end = -1, bool wait_levels = false, uint8_t* rgb_img = nullptr,
+                       int factor = 1) {
     const int nl = i_end < 0 ? c->d_n : i_end;
     const double N = n;
     char layer[64];
@@ -1275,6 +1277,11 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
                 Launch lp(c, s, layer, 2.0 * px2 * d.cs * d.cs * (conv_uses_wino43(cp, EPI_DEC, false) ? 2.25 : conv_uses_wino(cp, EPI_DEC, false) ? 4 : 9), 4.0 * px2 * d.cs * 3, 2.0 * px2 * d.cs * d.cs * 9);
                 HIP_TRY(launch_conv3x3(cp, EPI_DEC, false, n, s));
             }
+        } else if (factor > 1) {
+            snprintf(layer, sizeof layer, "d.final_%d_down", i);
+            Launch lp(c, s, layer, 2.0 * px * d.cs * d.in_c * 9, px * 4.0 * d.in_c + (mask ? px / (factor * factor) : 0.0));
+            HIP_TRY(launch_final_conv_down(i > s0 ? c->prev[i - 1] : nullptr, i > s0 ? d.F : 0, c->cvt[i], d.F, d.f_w, d.f_b, mask, n, R, R, d.cs,
+                                           factor, c->bf16, s));
         } else {
             snprintf(layer, sizeof layer, "d.final_%d", i);
             Launch lp(c, s, layer, 2.0 * px * d.cs * d.in_c * 9, px * (4.0 * d.in_c + (logits ? 4.0 * d.cs : 0) + (mask ? 1 : 0)));
@@ -1352,8 +1359,10 @@ int gsa_decoder_forward(gsa_ctx* c, void* stream, int32_t n, const float* const*
     return run_decoder(c, s, n, fsrc, nullptr, logits, mask);
 }
 
+// factor > 1: the pair at 1/factor resolution (gsa_generate_downscaled) -- toRGB runs as its own downscaling pass behind the generator
+// instead of riding on the last cvt convolution, and the final conv reduces the logits per block
 static int generate(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* dl, const float* const* noise, int32_t num_noise,
-                    uint8_t* img, uint8_t* mask) {
+                    uint8_t* img, uint8_t* mask, int factor = 1) {
     if (!noise) return fail(c, GSA_ERR_INVALID, "noise must not be null");
     if (num_noise != 2 * c->nlev) return fail(c, GSA_ERR_INVALID, "%d noise planes passed, this generator has %d", num_noise, 2 * c->nlev);
     if (c->d_n != c->nlev) return fail(c, GSA_ERR_INVALID, "decoder expects %d features, the generator yields %d", c->d_n, c->nlev);
@@ -1382,18 +1391,24 @@ static int generate(gsa_ctx* c, void* stream, int32_t n, const float* z, const f
     // that convolution is the lean 16 -> 16 kernel it writes the uint8 image as well (round 5): one 0.5 GB read per FFHQ batch of 8 less.
     // The last decoder level always runs on the caller's stream, behind the generator.
     bool fuse_rgb = false;
-    if (img && ns <= c->d_n - 1) {
+    if (img && ns <= c->d_n - 1 && factor == 1) {
         const int last = c->d_n - 1;
         ConvParams cp = cvt_params(c, last, fsrc[last], faff[last]);
         fuse_rgb = conv_fuses_torgb(cp, EPI_DEC, false, c->gc.channels);
     }
-    if (int rc = run_generator(c, s, n, z, dl, noise, nullptr, fuse_rgb ? nullptr : img, nullptr, ns > 0)) return rc;
+    if (int rc = run_generator(c, s, n, z, dl, noise, nullptr, fuse_rgb || factor > 1 ? nullptr : img, nullptr, ns > 0)) return rc;
+    if (img && factor > 1) {
+        const int l = c->nlev - 1, R = c->blk[l].R, C = c->blk[l].C, nc = c->gc.channels;
+        const double px = (double)n * R * R;
+        Launch lp(c, s, "g.torgb_down", 2.0 * px * C * nc, px * 4.0 * C + px / (factor * factor) * nc);
+        HIP_TRY(launch_torgb_down(c->x2[l], c->aff2[l], c->rgb_w, c->rgb_b, img, n, R, R, C, nc, factor, c->bf16, s));
+    }
     if (ns > 0) {
         if (int rc = run_decoder(c, c->side, n, fsrc, faff, nullptr, nullptr, 0, ns, true)) return rc;
         HIP_TRY(hipEventRecord(c->ev_join, c->side));
         HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
     }
-    return run_decoder(c, s, n, fsrc, faff, nullptr, mask, ns, -1, false, fuse_rgb ? img : nullptr);
+    return run_decoder(c, s, n, fsrc, faff, nullptr, mask, ns, -1, false, fuse_rgb ? img : nullptr, factor);
 }
 
 int gsa_generate(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* const* noise, int32_t num_noise, uint8_t* img,
@@ -1410,6 +1425,20 @@ int gsa_generate_w(gsa_ctx* c, void* stream, int32_t n, const float* dlatents, i
     if (!c->g_ready || !c->d_ready) return fail(c, GSA_ERR_STATE, "commit both generator and decoder first");
     if (int rc = check_dlatents(c, dlatents, num_layers)) return rc;
     return generate(c, stream, n, nullptr, dlatents, noise, num_noise, img, mask);
+}
+
+int gsa_generate_downscaled(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* dlatents, int32_t num_layers,
+                            const float* const* noise, int32_t num_noise, int32_t factor, uint8_t* img, uint8_t* mask) {
+    if (!c) return GSA_ERR_INVALID;
+    if (!c->g_ready || !c->d_ready) return fail(c, GSA_ERR_STATE, "commit both generator and decoder first");
+    if (!z == !dlatents) return fail(c, GSA_ERR_INVALID, "pass exactly one of z and dlatents");
+    if (dlatents)
+        if (int rc = check_dlatents(c, dlatents, num_layers)) return rc;
+    const int R = 4 << (c->nlev - 1);
+    if (factor != 1 && factor != 2 && factor != 4 && factor != 8)
+        return fail(c, GSA_ERR_INVALID, "downscale factor %d: 1, 2, 4 or 8 supported", factor);
+    if (R / factor < 16) return fail(c, GSA_ERR_INVALID, "downscale factor %d leaves %d px < 16 of the %d px output", factor, R / factor, R);
+    return generate(c, stream, n, z, dlatents, noise, num_noise, img, mask, factor);
 }
 
 int gsa_fill_inputs(gsa_ctx* c, void* stream, int32_t n, uint64_t seed, uint64_t first_index, float* z, float* const* noise,

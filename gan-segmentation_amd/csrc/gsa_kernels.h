@@ -134,6 +134,12 @@ hipError_t launch_styles_dlatents(const float* dlatents, const float* avg, const
                                   const int4* tiles, int num_tiles, float* styles, int n, int K, int J, int NL, hipStream_t s);
 hipError_t launch_torgb(const float* x, const Aff* aff, const float* w, const float* b, float* rgb,
                         uint8_t* img, int n, int H, int W, int C, int nc, int bf16, hipStream_t s);
+// gsa_downscale.hip: the image and the mask at 1/f resolution (f in {2, 4, 8}): toRGB's u reduced over each
+// f x f block in the quad-tree order (img: (N, H/f, W/f, nc) u8), and the final conv's per-class block sums -> argmax (mask: (N, H/f, W/f))
+hipError_t launch_torgb_down(const float* x, const Aff* aff, const float* w, const float* b, uint8_t* img, int n, int H, int W, int C,
+                             int nc, int f, int bf16, hipStream_t s);
+hipError_t launch_final_conv_down(const float* src0, int C0, const float* src1, int C1, const float* wpk, const float* bias, uint8_t* mask,
+                                  int n, int H, int W, int ncls, int f, int bf16, hipStream_t s);
 hipError_t launch_export_nchw(const float* x, const Aff* aff, float* out, int n, int H, int W, int C, int bf16, hipStream_t s);
 hipError_t launch_import_nhwc(const float* in, float* out, int n, int H, int W, int C, int bf16, hipStream_t s);
 hipError_t launch_final_conv(const float* src0, int C0, const float* src1, int C1, const float* wpk,

@@ -15,6 +15,11 @@ The two StyleGAN sampling controls: ``truncation_psi`` replaces the weight file'
 shard-invariant plan of ``style_mix``, through the per-layer (W-space) step ``gsa_generate_w``.  ``generate_batch_w`` runs that
 step on caller-made dlatents.  The W path runs eager: it is never captured into a hipGraph.  With the defaults every call runs
 the z path exactly as before.
+
+``output_downscale`` (1, 2, 4 or 8; fixed at construction) makes every fused call -- ``generate_batch``, ``generate_batch_w``,
+``generate_indexed``, style-mixed or not -- return the pair at R/f through ``gsa_generate_downscaled``: the image is the mean of
+toRGB's fp32 values over each f x f block before the uint8 truncation, the mask the argmax of the block-summed logits (the rule of
+include/gsa.h and DESIGN.md section 11).  ``get_images`` and everything that feeds the annotator or the decoder stay full size.
 """
 import os
 
@@ -34,11 +39,13 @@ _GRAPH_CAPTURES_MAX = 16
 
 class ImageGenerator:
     style_mix_prob = 0.0
+    output_downscale = 1
 
     def __init__(self, gpu_ids, gan_dir, gan="ffhq", batch_size=4, return_latents=False, seed=0, precision="fp32",
-                 truncation_psi=None, style_mix_prob=0.0):
+                 truncation_psi=None, style_mix_prob=0.0, output_downscale=1):
         max_res_log2_dict = _weights.GAN_MAX_RES_LOG2
         self.max_res_log2 = max_res_log2_dict[gan]
+        self.output_downscale = self.check_output_downscale(output_downscale, self.max_res_log2)
         self.latent_size = 512
         self.return_latents = return_latents
         self.batch_size = batch_size
@@ -68,10 +75,11 @@ class ImageGenerator:
 
     @classmethod
     def from_params(cls, gcfg, gparams, dcfg=None, dparams=None, gpu_ids=(0,), batch_size=4,
-                    return_latents=False, seed=0, precision="fp32", truncation_psi=None, style_mix_prob=0.0):
+                    return_latents=False, seed=0, precision="fp32", truncation_psi=None, style_mix_prob=0.0, output_downscale=1):
         """Build from in-memory weights (tests, benchmarks: no pretrained files exist here)."""
         self = cls.__new__(cls)
         self.max_res_log2 = gcfg["max_res_log2"]
+        self.output_downscale = cls.check_output_downscale(output_downscale, self.max_res_log2)
         self.latent_size = gcfg["latent_size"]
         self.return_latents = return_latents
         self.batch_size = batch_size
@@ -101,6 +109,18 @@ class ImageGenerator:
         if not 0.0 <= p <= 1.0:
             raise ValueError("style_mix_prob must be in [0, 1], got %r" % p)
         return p
+
+    @staticmethod
+    def check_output_downscale(f, max_res_log2):
+        """The output downscale factor f as an int: 1, 2, 4 or 8, leaving at least 16 px of the 2**max_res_log2 output
+        (ValueError otherwise)."""
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or int(f) not in (1, 2, 4, 8):
+            raise ValueError("output_downscale must be 1, 2, 4 or 8, got %r" % (f,))
+        f = int(f)
+        if (2 ** max_res_log2) // f < 16:
+            raise ValueError("output_downscale %d leaves %d px of the %d px output (at least 16 needed)"
+                             % (f, (2 ** max_res_log2) // f, 2 ** max_res_log2))
+        return f
 
     def _get_G(self, config, device):
         return Generator(config, device=device, precision=self.precision)
@@ -223,7 +243,7 @@ class ImageGenerator:
         return torch.where(sel[:, :, None], w_b[:, None, :], w_a[:, None, :]).contiguous(), noise
 
     def _check_out(self, out, n, dev):
-        R, nc = 2 ** self.max_res_log2, self.netG.nc
+        R, nc = 2 ** self.max_res_log2 // self.output_downscale, self.netG.nc
         img, mask = out
         for t, shape in ((img, (n, R, R, nc)), (mask, (n, R, R))):
             if tuple(t.shape) != shape or t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
@@ -236,7 +256,7 @@ class ImageGenerator:
         z, noise, n = g._prepare(z, noise)
         model = g._model
         dev = model.device
-        R = 2 ** self.max_res_log2
+        R = 2 ** self.max_res_log2 // self.output_downscale
         if out is None:
             img = torch.empty((n, R, R, g.nc), device=dev, dtype=torch.uint8)
             mask = torch.empty((n, R, R), device=dev, dtype=torch.uint8)
@@ -251,7 +271,7 @@ class ImageGenerator:
             # epoch changes whenever the context's workspace, weights or stream structure change AND whenever a call of the
             # context failed (a failed pass leaves statistic rows the next EAGER pass re-zeroes -- a replay would not).
             key = (n, z.data_ptr(), tuple(nptrs), img.data_ptr(), mask.data_ptr(), torch.cuda.current_stream(dev).cuda_stream,
-                   model.ctx.graph_epoch)
+                   model.ctx.graph_epoch, self.output_downscale)
             cache = model.__dict__.setdefault("_graphs", {})
             hit = cache.get(key)
             if hit is not None:
@@ -268,31 +288,43 @@ class ImageGenerator:
                     cache.pop(next(iter(cache)))
                 if len(seen) > 64:
                     seen.clear()
-                graph = self._capture(model, dev, n, z, nptrs, img, mask)
+                graph = self._capture(model, dev, n, z, nptrs, img, mask, self.output_downscale)
                 model.__dict__["_graph_captures"] = model.__dict__.get("_graph_captures", 0) + 1      # only a capture that succeeded counts
                 graph.replay()
                 cache[key] = graph
                 return img, mask
-        model.ctx.generate(current_stream_ptr(dev), n, z.data_ptr(), nptrs, img.data_ptr(), mask.data_ptr())
+        self._step(model.ctx, current_stream_ptr(dev), n, z, nptrs, img, mask, self.output_downscale)
         return img, mask
+
+    @staticmethod
+    def _step(ctx, stream, n, z, nptrs, img, mask, factor):
+        """One fused z step: gsa_generate, or gsa_generate_downscaled when the pair is written at 1/factor resolution."""
+        if factor == 1:
+            ctx.generate(stream, n, z.data_ptr(), nptrs, img.data_ptr(), mask.data_ptr())
+        else:
+            ctx.generate_downscaled(stream, n, z.data_ptr(), None, 0, nptrs, factor, img.data_ptr(), mask.data_ptr())
 
     def _generate_on_w(self, r, dlatents, noise, out=None):
         """The fused step from per-layer dlatents on replica ``r`` (gsa_generate_w); always eager."""
         g = self._gens[r]
         dl, noise, n = g._prepare_w(dlatents, noise)
         dev = g._model.device
-        R = 2 ** self.max_res_log2
+        R = 2 ** self.max_res_log2 // self.output_downscale
         if out is None:
             img = torch.empty((n, R, R, g.nc), device=dev, dtype=torch.uint8)
             mask = torch.empty((n, R, R), device=dev, dtype=torch.uint8)
         else:
             img, mask = self._check_out(out, n, dev)
-        g._model.ctx.generate_w(current_stream_ptr(dev), n, dl.data_ptr(), g.num_style_layers, [a.data_ptr() for a in noise],
-                                img.data_ptr(), mask.data_ptr())
+        nptrs = [a.data_ptr() for a in noise]
+        if self.output_downscale == 1:
+            g._model.ctx.generate_w(current_stream_ptr(dev), n, dl.data_ptr(), g.num_style_layers, nptrs, img.data_ptr(), mask.data_ptr())
+        else:
+            g._model.ctx.generate_downscaled(current_stream_ptr(dev), n, None, dl.data_ptr(), g.num_style_layers, nptrs,
+                                             self.output_downscale, img.data_ptr(), mask.data_ptr())
         return img, mask
 
     @staticmethod
-    def _capture(model, dev, n, z, nptrs, img, mask):
+    def _capture(model, dev, n, z, nptrs, img, mask, factor=1):
         """Capture one fused step into a hipGraph on a capture stream of our own: ``CUDAGraph.capture_begin/capture_end``
         directly -- not the ``torch.cuda.graph`` context manager, whose device-wide synchronize, ``gc.collect`` and
         ``empty_cache()`` would stall the caller's steady loop and could move its recycled tensors to new addresses."""
@@ -305,7 +337,7 @@ class ImageGenerator:
         with torch.cuda.stream(side):
             graph.capture_begin(capture_error_mode="thread_local")
             try:
-                model.ctx.generate(side.cuda_stream, n, z.data_ptr(), nptrs, img.data_ptr(), mask.data_ptr())
+                ImageGenerator._step(model.ctx, side.cuda_stream, n, z, nptrs, img, mask, factor)
             except BaseException:
                 # the step failed while it was being recorded: end the (now invalid) capture, but let the ORIGINAL error through --
                 # capture_end raises on an invalidated capture and would hide it
@@ -384,7 +416,7 @@ class ImageGenerator:
         return img, mask
 
     def generate_batch(self, z, noise=None, out=None):
-        """latents (N,512) [+ noise planes] -> (img (N,R,R,3) u8, mask (N,R,R) u8) on the GPU.
+        """latents (N,512) [+ noise planes] -> (img (N,R,R,3) u8, mask (N,R,R) u8) on the GPU (R/f with output_downscale f).
         The per-batch body of ``main.py generate`` (reference main.py:97-99) in one call.
         ``out=(img, mask)``: write into these contiguous uint8 device tensors instead of new ones
         (e.g. the fused send buffer of ``dist.PairGatherer``).  With several gpu ids the batch is split over the

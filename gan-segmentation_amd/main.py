@@ -4,7 +4,8 @@ with the same ``config.yml`` keys (reference config.yml.example:1-8); `generate`
 is out of scope.
 
 Writes ``img_%06d.jpg`` (RGB image; the reference flips to BGR only because cv2 expects it)
-and ``mask_%06d.png`` (single channel, class index) into BASE_DIR/dataset/train_generated.
+and ``mask_%06d.png`` (single channel, class index) into BASE_DIR/dataset/train_generated, at R/f px with the additive
+key ``OUTPUT_DOWNSCALE: f`` (1, 2, 4 or 8; default 1).
 With torchrun (one process per GPU) the sample indices are sharded across ranks and every rank
 writes its own files -- no collective is needed when the sink is the filesystem.
 """
@@ -67,6 +68,8 @@ def generate(cfg, limit=None, workers=None):
     precision = cfg.get("PRECISION", "fp32")   # additive key: "bf16" = bf16 MFMA operands (BASELINE config 5)
     truncation_psi = cfg.get("TRUNCATION_PSI")                # additive key: replaces the weight file's truncation vector
     style_mix_prob = float(cfg.get("STYLE_MIX_PROB", 0.0))    # additive key: share of style-mixed samples (style_mix.py)
+    # additive key: write the pairs at R/f (box-filtered image, block-summed logits' argmax); checked before any model is loaded
+    downscale = ImageGenerator.check_output_downscale(cfg.get("OUTPUT_DOWNSCALE", 1), GAN_MAX_RES_LOG2[gan])
 
     solver = SegSolver(GAN_MAX_RES_LOG2[gan], os.path.join(root_dir, "data"), os.path.join(root_dir, "checkpoints"),
                        gpu_ids=solver_ids, keep_weights=False, precision=precision)
@@ -74,7 +77,7 @@ def generate(cfg, limit=None, workers=None):
         print("train Decoder first!")   # reference main.py:82-84
         return -1
     netG = ImageGenerator(gpu_ids=gan_ids, gan_dir=gan_dir, gan=gan, batch_size=batch, precision=precision,
-                          truncation_psi=truncation_psi, style_mix_prob=style_mix_prob)
+                          truncation_psi=truncation_psi, style_mix_prob=style_mix_prob, output_downscale=downscale)
     netG.attach_decoder(solver.cfg, solver.net)
     dst_dir = os.path.join(root_dir, "dataset", "train_generated")
     os.makedirs(dst_dir, exist_ok=True)

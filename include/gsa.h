@@ -30,8 +30,9 @@
  *  - tensors crossing the boundary use the reference's layouts: fp32 NCHW activations,
  *    OIHW conv weights, (N,H,W,3) u8 RGB images, (N,H,W) u8 masks.
  *
- * The same signatures with the prefix `gsao_` (the W-space entries excepted) are exported by the CPU oracle
- * (oracle/c/gsa_oracle.c, test infrastructure only) with every pointer a host pointer.
+ * The same signatures with the prefix `gsao_` (the downscaled entry excepted: its tests apply the rule stated there to the
+ * oracle's full-size outputs) are exported by the CPU oracle (oracle/c/gsa_oracle.c, test infrastructure only) with every
+ * pointer a host pointer.
  */
 #ifndef GSA_H
 #define GSA_H
@@ -158,6 +159,20 @@ int gsa_generator_forward_w(gsa_ctx* ctx, void* stream, int32_t n, const float* 
 /* gsa_generate with per-layer latents: bitwise identical to gsa_generator_forward_w + gsa_decoder_forward. */
 int gsa_generate_w(gsa_ctx* ctx, void* stream, int32_t n, const float* dlatents, int32_t num_layers,
                    const float* const* noise, int32_t num_noise, uint8_t* img, uint8_t* mask);
+
+/* --- downscaled pairs ------------------------------------------------------------------------------------------------------
+ * The fused step with the pair written at 1/factor resolution, factor in {1, 2, 4, 8}, from the fp32 values the full-size
+ * entries stop at.  Output pixel (Y, X) covers rows factor*Y .. factor*Y+factor-1 and the same columns; the block sum S_f is a
+ * pairwise quad tree in fp32, S_2s(top-left) = (S_s(TL) + S_s(TR)) + (S_s(BL) + S_s(BR)), every add rounded:
+ *   img  dev (N, R/factor, R/factor, channels) u8: (uint8_t)(S_f(u) * (1/factor^2)) with u = 255 * clamp((v + 1) / 2, 0, 1) of
+ *        the toRGB value v -- the fp32 value the full-size image truncates -- so the mean is taken before the truncation;
+ *   mask dev (N, R/factor, R/factor) u8: the first maximum over classes of S_f(logit).
+ * Exactly one of z (N, latent_size) and dlatents (N, num_layers, latent_size) is non-null; dlatents is checked as in
+ * gsa_generate_w.  A factor outside {1, 2, 4, 8} or an output under 16 px is GSA_ERR_INVALID.  factor 1 is gsa_generate (z) or
+ * gsa_generate_w (dlatents) bit for bit; the decoder levels overlap the synthesis on the second stream as there.  Needs no
+ * workspace beyond gsa_reserve's. */
+int gsa_generate_downscaled(gsa_ctx* ctx, void* stream, int32_t n, const float* z, const float* dlatents, int32_t num_layers,
+                            const float* const* noise, int32_t num_noise, int32_t factor, uint8_t* img, uint8_t* mask);
 
 /* gsa_generate runs the decoder on a second HIP stream beside the synthesis of the higher
  * resolutions (fork/join through events).  `levels` = number of decoder levels placed there; negative = the default:
