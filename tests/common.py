@@ -76,3 +76,14 @@ def golden_bench_outputs():
 def pair_digest(img, mask):
     import hashlib
     return hashlib.sha256(np.ascontiguousarray(img).tobytes() + np.ascontiguousarray(mask).tobytes()).hexdigest()
+
+
+SWEEP_MAX_BATCH = 64
+
+
+def sweep_setup(gan):
+    """tests/test_gpu_batch_sweep.py's model and inputs: the full-size config with z-dependent mapping weights (lively) and
+    SWEEP_MAX_BATCH distinct samples (inputs seeds 3000 / 4000).  Sample 0 is what tests/golden/sweep_anchors.json digests."""
+    gcfg, gp, dcfg, dp, _z, _noise = gan_setup(gan, 1, live_mapping=True)
+    z, noise = W.synthetic_inputs(gcfg, SWEEP_MAX_BATCH, seed_z=3000, seed_noise=4000)
+    return gcfg, gp, dcfg, dp, z, noise

@@ -344,8 +344,9 @@ def test_decoder_start_res_bit_exact(torch_cuda, oracle_lib, start_res, use_bn):
 @pytest.mark.parametrize("batch", [8, 4])
 def test_benchmarked_config_ffhq(torch_cuda, batch):
     """What bench.py times -- BASELINE.json configs[1] (ffhq 1024^2, batch 8) and the per-GPU share of configs[2]
-    (batch 4) on bench.py's own inputs.  Kernel selection depends on the batch (tile geometry, persistent forms,
-    the stream-overlap rule flips at 8), so these batch sizes are checked themselves: the first samples against the
+    (batch 4) on bench.py's own inputs.  Kernel selection depends on the batch (tile geometry, persistent forms;
+    the stream-overlap rule does not: every decoder level below the last goes to the side stream at every batch), so these
+    batch sizes are checked themselves: the first samples against the
     C oracle's digests (tests/golden/bench_outputs.json), every sample against what batches of 1 and 2 produce
     (batch composition), with the decoder-beside-synthesis overlap off, on and by the default rule."""
     from tests.common import bench_setup, golden_bench_outputs, pair_digest
