@@ -20,12 +20,16 @@ the z path exactly as before.
 ``generate_indexed``, style-mixed or not -- return the pair at R/f through ``gsa_generate_downscaled``: the image is the mean of
 toRGB's fp32 values over each f x f block before the uint8 truncation, the mask the argmax of the block-summed logits (the rule of
 include/gsa.h and DESIGN.md section 11).  ``get_images`` and everything that feeds the annotator or the decoder stay full size.
+
+``training_batches`` is the consumer side without files: an iterator of augmented, normalised NCHW batches with their labels, made
+on the GPU from ``generate_indexed`` pairs by the plan and the kernel of ``augment``.
 """
 import os
 
 import numpy as np
 import torch
 
+from . import augment as _augment
 from . import style_mix as _style_mix
 from . import weights as _weights
 from ._runtime import current_stream_ptr, split_sizes, to_device_f32
@@ -217,6 +221,50 @@ class ImageGenerator:
                 z, noise = g.draw_indexed(first_index + lo, hi - lo, seed)
                 parts.append(self._generate_on(r, z, noise))
         return self._collect(parts, n, out)
+
+    def training_batches(self, batch, crop=480, mode="train", seed=0, first_index=0, num_samples=None, rank=0, world=1,
+                         mean=_augment.IMAGENET_MEAN, std=_augment.IMAGENET_STD, dtype=torch.float32, labels="uint8",
+                         ignore_label=_augment.IGNORE_LABEL, **limits):
+        """The training stream: an iterator of ``(image (n, C, crop, crop) dtype, label (n, crop, crop), first_index)``.
+
+        Batch k of the global sequence holds the samples ``first_index + k*batch ..`` and goes to the rank with ``k % world == rank``
+        (``augment.stream_batches``); ``num_samples=None`` streams without end, otherwise the last batch is short.  Every batch is
+        ``generate_indexed`` of its indices (so precision, truncation, style mixing, ``output_downscale`` and several gpu ids work
+        as there), warped by ``augment.plan_matrices(seed, index, ...)`` (``mode``: "train" or "center"; ``limits``: flip, rotate,
+        scale, shift; ``crop=None`` keeps the pair's size) and normalised with ``mean`` / ``std`` by one kernel on the same stream.
+        ``dtype``: torch.float32 or torch.bfloat16.  ``labels="uint8"`` keeps ``ignore_label`` (255) outside the image;
+        ``labels="int64"`` maps it to -1 as the reference's loader does.  The yielded tensors are new every batch and ordered on
+        the caller's current stream: the consumer may keep them.  Arguments are checked here, before any GPU work."""
+        if self._decoder is None:
+            raise RuntimeError("attach_decoder() first")
+        crop, mode = _augment.check_crop(crop), _augment.check_mode(mode)
+        if labels not in ("uint8", "int64"):
+            raise ValueError("labels must be \"uint8\" or \"int64\", got %r" % (labels,))
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dtype must be torch.float32 or torch.bfloat16, got %r" % (dtype,))
+        if not 0 <= int(ignore_label) <= 255:
+            raise ValueError("ignore_label must be in 0..255, got %r" % (ignore_label,))
+        R, nc = 2 ** self.max_res_log2 // self.output_downscale, self.netG.nc
+        out_size = _augment.check_shapes(R, R, nc, _augment.output_size(R, R, crop))
+        scale, bias = _augment.normalisation(mean, std)
+        if len(scale) != nc:
+            raise ValueError("mean and std need one value per image channel (%d), got %d" % (nc, len(scale)))
+        _augment.plan_matrices(seed, first_index, 0, R, R, crop, mode, **limits)        # the limits' own checks
+        batches = _augment.stream_batches(first_index, batch, num_samples, rank, world)
+        return self._training_batches(batches, seed, R, crop, mode, limits, out_size, scale, bias, dtype, labels, int(ignore_label))
+
+    def _training_batches(self, batches, seed, R, crop, mode, limits, out_size, scale, bias, dtype, labels, ignore_label):
+        dev0 = self._gens[0]._model.device
+        for first, n in batches:
+            img, mask = self.generate_indexed(first, n, seed=seed)
+            matrices = _augment.plan_matrices(seed, first, n, R, R, crop, mode, **limits)
+            with torch.cuda.device(dev0):
+                image, label = _augment.augment_pairs(img, mask, matrices, out_size, scale=scale, bias=bias, dtype=dtype,
+                                                      ignore_label=ignore_label)
+                if labels == "int64":
+                    label = label.to(torch.int64)
+                    label[label == ignore_label] = -1
+            yield image, label, first
 
     def _generate_indexed_mixed(self, first_index, n, seed, out):
         if self._decoder is None:
