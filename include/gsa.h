@@ -203,7 +203,9 @@ int gsa_fill_inputs(gsa_ctx* ctx, void* stream, int32_t n, uint64_t seed, uint64
 /* Per-batch arithmetic of SegSolver.evaluate_for_data (reference seg_solver.py:229-262) and
  * SegmentationMetric.update (reference metrics.py:497-606), SURVEY.md section 8f-4:
  *   logits     dev (N,classes,H,W) fp32 (gsa_decoder_forward's logits)
- *   labels     dev (N,H,W) int8: class index, -1 = ignore (seg_datasets.py:85-106)
+ *   labels     dev (N,H,W) int8: class index, -1 = ignore (seg_datasets.py:85-106).  Every value outside 0..classes-1
+ *              is treated like -1, silently: the pixel adds no count and no loss (a mask written for more classes
+ *              than the decoder has is not an error here; the caller validates its labels if it needs to)
  *   confusion  dev [classes*classes] u64, ACCUMULATED: confusion[l*classes+p] += #pixels with label l >= 0 and
  *              argmax p (first maximum).  pixAcc / IoU follow from it: correct = trace, labelled = sum,
  *              inter = diagonal, union = row sum + column sum - diagonal.

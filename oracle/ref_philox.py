@@ -24,8 +24,10 @@ def philox4x32_10(ctr, key):
     return np.stack(c, axis=-1).astype(np.uint32)
 
 
-def fill_normal(n, per_sample, first_index, plane, seed):
-    """-> (n, per_sample) fp32, the values fill_normal_kernel writes (up to libm rounding)."""
+def uniforms(n, per_sample, first_index, plane, seed):
+    """-> (n, per_sample // 4, 4) fp32: the uniforms in (0, 1] the kernel feeds to Box-Muller, u = (x >> 8 + 0.5) * 2^-24 of the
+    Philox words x.  Conversion, sum and product are single correctly rounded fp32 operations, so these are the device's values
+    exactly (the sum rounds to 24 bits: the largest word gives u = 1)."""
     quads = per_sample // 4
     ctr = np.zeros((n, quads, 4), np.uint32)
     ctr[..., 0] = np.arange(quads, dtype=np.uint32)[None, :]
@@ -34,8 +36,13 @@ def fill_normal(n, per_sample, first_index, plane, seed):
     ctr[..., 2] = (idx & MASK).astype(np.uint32)[:, None]
     ctr[..., 3] = (idx >> np.uint64(32)).astype(np.uint32)[:, None]
     x = philox4x32_10(ctr, (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
-    u = ((x >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
-    out = np.empty((n, quads, 4), np.float32)
+    return ((x >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+
+
+def fill_normal(n, per_sample, first_index, plane, seed):
+    """-> (n, per_sample) fp32, the values fill_normal_kernel writes (up to libm rounding)."""
+    u = uniforms(n, per_sample, first_index, plane, seed)
+    out = np.empty(u.shape, np.float32)
     for h in range(2):
         r = np.sqrt(np.float32(-2.0) * np.log(u[..., 2 * h]), dtype=np.float32)
         a = np.float32(6.283185307179586) * u[..., 2 * h + 1]

@@ -78,12 +78,26 @@ def pair_digest(img, mask):
     return hashlib.sha256(np.ascontiguousarray(img).tobytes() + np.ascontiguousarray(mask).tobytes()).hexdigest()
 
 
-SWEEP_MAX_BATCH = 64
+SWEEP_MAX_BATCH = 64      # every model is swept over 1..64, and the first 64 sweep inputs are one draw (sweep_setup)
+
+# The largest batch tests/test_gpu_batch_sweep.py and tests/dispatch_map.py run per model.  Beyond 64 only the batch is new: bedrooms at
+# 256 (64 channels x 256^2 px) and cars at 128 (32 x 512^2) hold 2^30 elements in their largest tensor, exactly what ffhq holds at 64
+# (16 x 1024^2), and ffhq stays there.  Workspace gsa_reserve asks for at these batches, from its sizing code (fp32, generator + decoder,
+# summed over its dev_alloc calls: activations x2 / t_raw / x1, decoder din / cvt / ya / prev / scb, and the small rows): bedrooms 256:
+# 33 GiB, cars 128: 42 GiB, ffhq 64: 46 GiB -- each below a third of the card's 288 GB, so no maximum is halved.
+SWEEP_MAX = {"ffhq": 64, "cars": 128, "bedrooms": 256}
 
 
 def sweep_setup(gan):
     """tests/test_gpu_batch_sweep.py's model and inputs: the full-size config with z-dependent mapping weights (lively) and
-    SWEEP_MAX_BATCH distinct samples (inputs seeds 3000 / 4000).  Sample 0 is what tests/golden/sweep_anchors.json digests."""
+    SWEEP_MAX[gan] distinct samples.  Samples 0..63 are one draw (inputs seeds 3000 / 4000) whatever the maximum is -- the noise planes
+    of a draw depend on its batch size, and sample 0 is what tests/golden/sweep_anchors.json digests; samples 64.. are a second draw
+    (seeds 3001 / 4001)."""
     gcfg, gp, dcfg, dp, _z, _noise = gan_setup(gan, 1, live_mapping=True)
     z, noise = W.synthetic_inputs(gcfg, SWEEP_MAX_BATCH, seed_z=3000, seed_noise=4000)
+    more = SWEEP_MAX[gan] - SWEEP_MAX_BATCH
+    if more > 0:
+        z2, noise2 = W.synthetic_inputs(gcfg, more, seed_z=3001, seed_noise=4001)
+        z = np.concatenate([z, z2])
+        noise = [np.concatenate([a, b]) for a, b in zip(noise, noise2)]
     return gcfg, gp, dcfg, dp, z, noise

@@ -8,19 +8,21 @@ same kernel look the same here (tests/test_gpu_batch_sweep.py lists those thresh
 
     python -m tests.dispatch_map [gan] [precision]
 
-prints the batches in 1..64 at which the map changes, and what changes there.
+prints the batches in 1..SWEEP_MAX[gan] (tests/common.py: ffhq 64, cars 128, bedrooms 256) at which the map changes, and what changes there.
 """
 import sys
 
 import numpy as np
 
-from tests.common import SWEEP_MAX_BATCH, sweep_setup
+from tests.common import SWEEP_MAX, sweep_setup
 
 PATHS = ("generate", "two_call")
 
 
-def build(gan, precision, batch=SWEEP_MAX_BATCH):
-    """One ImageGenerator reserved for `batch`, eager (no hipGraph replay), and its sweep inputs on the device once."""
+def build(gan, precision, batch=None):
+    """One ImageGenerator reserved for `batch` (default: the model's sweep maximum), eager (no hipGraph replay), and its sweep inputs
+    on the device once."""
+    batch = SWEEP_MAX[gan] if batch is None else batch
     import torch
     from gan_segmentation_amd.image_generator import ImageGenerator
     gcfg, gp, dcfg, dp, z, noise = sweep_setup(gan)
@@ -77,10 +79,10 @@ def main(argv):
     gan = argv[0] if len(argv) > 0 else "ffhq"
     precision = argv[1] if len(argv) > 1 else "fp32"
     gen, z, noise = build(gan, precision)
-    maps = {b: dispatch_map(gen, z, noise, b) for b in range(1, SWEEP_MAX_BATCH + 1)}
+    maps = {b: dispatch_map(gen, z, noise, b) for b in range(1, SWEEP_MAX[gan] + 1)}
     bps = breakpoints(maps)
     print("%s %s: %d (layer, kernel) pairs over batches 1..%d; the map changes at %s" % (
-        gan, precision, len(frozenset().union(*maps.values())), SWEEP_MAX_BATCH, [b for b, _, _ in bps]))
+        gan, precision, len(frozenset().union(*maps.values())), SWEEP_MAX[gan], [b for b, _, _ in bps]))
     for b, added, removed in bps:
         print("batch %d:" % b)
         for layer, kernel in added:

@@ -1,4 +1,5 @@
-"""Float64 CPU references and comparison rules for the decoder-training kernels (include/gsa_train.h).
+"""Float64 CPU references and comparison rules for the decoder-training kernels (include/gsa_train.h) and, at the end, float64
+references of the counter-based inputs (gsa_fill_inputs) and of the evaluation kernel (gsa_segmentation_eval).
 
 Two ways of comparing a kernel result with its reference:
 
@@ -145,3 +146,60 @@ def wgrad_tiles_per_block(n, Cin, Cout, H, W):
     pairs = ((Cout + 15) // 16) * ((Cin + 15) // 16)
     gx = max(1, min((WGRAD_BLOCKS + pairs - 1) // pairs, work))
     return work // gx
+
+
+# ---- float64 references of the kernels around the convolution path --------------------------------------------------
+# numpy only; the references above need torch's autograd, these are plain formulas.
+def box_muller_f64(u):
+    """The transform of fill_normal_kernel in float64.  u: (..., 4) uniforms in (0, 1] -- oracle/ref_philox.uniforms, the fp32
+    values the kernel forms from the Philox words (their integer stream is pinned by the Random123 known-answer vectors of
+    tests/test_philox.py); they are taken as exact, and everything after them -- the logarithm, the root, 2 pi u, cosine, sine
+    and the products -- is float64 here and fp32 in the kernel and in oracle/ref_philox.fill_normal.
+    -> (..., 4) float64: (r0 cos a0, r0 sin a0, r1 cos a1, r1 sin a1) with r = sqrt(-2 ln u_even), a = 2 pi u_odd."""
+    import numpy as np
+    u = np.asarray(u, np.float64)
+    out = np.empty(u.shape, np.float64)
+    for h in range(2):
+        r = np.sqrt(-2.0 * np.log(u[..., 2 * h]))
+        a = (2.0 * np.pi) * u[..., 2 * h + 1]
+        out[..., 2 * h] = r * np.cos(a)
+        out[..., 2 * h + 1] = r * np.sin(a)
+    return out
+
+
+def fill_normal_f64(n, per_sample, first_index, plane, seed):
+    """-> (n, per_sample) float64: what gsa_fill_inputs writes for (seed, plane, samples first_index ..), in float64."""
+    from oracle import ref_philox
+    return box_muller_f64(ref_philox.uniforms(n, per_sample, first_index, plane, seed)).reshape(n, per_sample)
+
+
+# the largest |x| Box-Muller can give: the smallest uniform is (0 + 0.5) * 2^-24 = 2^-25; the factor allows for the fp32 roundings of
+# the logarithm, the root and the product
+NORMAL_ABS_MAX = math.sqrt(-2.0 * math.log(2.0 ** -25)) * (1.0 + 2.0 ** -20)
+
+
+def weighted_softmax_ce_f64(logits, labels):
+    """(N,K,H,W) logits, (N,H,W) integer labels -> (N,) float64: the mean over ALL H*W pixels of -log_softmax(logits)[label] on the
+    pixels whose label is in 0..K-1 and 0 elsewhere (-1 = ignore; a label >= K counts as ignored, as gsa_segmentation_eval
+    treats it).  Every step in float64, one sample at a time."""
+    import numpy as np
+    N, K = logits.shape[:2]
+    out = np.zeros(N, np.float64)
+    for i in range(N):
+        x = logits[i].astype(np.float64).reshape(K, -1)
+        lab = np.asarray(labels[i]).reshape(-1).astype(np.int64)
+        ok = (lab >= 0) & (lab < K)
+        m = x.max(axis=0)
+        lse = m + np.log(np.exp(x - m).sum(axis=0))
+        picked = np.take_along_axis(x, np.clip(lab, 0, K - 1)[None], axis=0)[0]
+        out[i] = np.where(ok, lse - picked, 0.0).sum() / lab.size
+    return out
+
+
+def confusion_i64(logits, labels, K):
+    """-> (K, K) int64: counts of (label, argmax) over the pixels whose label is in 0..K-1; argmax takes the first maximum."""
+    import numpy as np
+    pred = np.argmax(logits, axis=1).reshape(-1)
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    ok = (lab >= 0) & (lab < K)
+    return np.bincount(lab[ok] * K + pred[ok], minlength=K * K).reshape(K, K).astype(np.int64)

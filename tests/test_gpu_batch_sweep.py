@@ -4,10 +4,12 @@ DESIGN.md section 1: the dataset is byte-identical for any batch size, rank coun
 (Winograd, K-split and sub-pixel rules depend on a layer's shape only), but the launch form that runs a layer depends on the batch
 size n: pick_geom, launch_conv_t, subpixel_cout_tile / subpixel_res_lds / subpixel_wst_lds, launch_wino_t, the persistent tile ranges
 of gsa_wino_lean.hip's launch_t / launch_stream_t, bf16_lean_nt.  The reduced configurations (<= 64 channels) never reach the forms of
-the 256- and 512-channel layers, so this module runs ffhq 1024, cars 512 and bedrooms 256 at every batch of SWEEP, in both modes:
+the 256- and 512-channel layers, so this module runs ffhq 1024, cars 512 and bedrooms 256 at every batch of SWEEP -- and cars up to 128 and
+bedrooms up to 256 samples at the batches of SWEEP_BEYOND (tests/common.py SWEEP_MAX) -- in both modes:
 
- * coverage guard: the (layer, kernel) pairs of SWEEP's batches include every pair any batch in 1..64 launches (tests/dispatch_map.py);
- * batch composition: every sample of every SWEEP batch has the bytes of the same sample run alone (torch.equal on the device) --
+ * coverage guard: the (layer, kernel) pairs of the model's sweep batches include every pair any batch in 1..SWEEP_MAX[gan] launches
+   (tests/dispatch_map.py);
+ * batch composition: every sample of every sweep batch has the bytes of the same sample run alone (torch.equal on the device) --
    the fused step's u8 pair, the two-call path's fp32 rgb and logits, and all features of the batch's first and last sample;
  * the batch-1 run against the C oracle: the digests of tests/golden/sweep_anchors.json (fp32), the contract of
    tests/test_gpu_bf16.py against Oracle(precision="bf16") (bf16);
@@ -24,7 +26,7 @@ import numpy as np
 import pytest
 
 from tests import dispatch_map as DM
-from tests.common import SWEEP_MAX_BATCH, gan_setup, sweep_setup
+from tests.common import SWEEP_MAX, gan_setup, sweep_setup
 from tests.test_downscale_host import rule_image, rule_mask
 from tests.test_gpu_bf16 import _check_against, check_first_level
 
@@ -57,6 +59,40 @@ SWEEP = [
     63, 64,  # map 63/64: g.16.conv_1 / d.main_3.a streamed (fp32: the lean sub-pixel kernel), pick_geom of d.main_2.b and the bf16 g.16.conv_2
 ]
 
+# Beyond 64 (tests/common.py SWEEP_MAX: cars to 128, bedrooms to 256, ffhq stays at 64): both sides of every batch at which the measured
+# map of the model changes there, in either mode, plus 65, 128, 129 and the maximum.  Measured (`python -m tests.dispatch_map <gan> <precision>`,
+# MI355X): beyond 64 the map changes at 128 for cars and at 128 and 256 for bedrooms, in fp32 and in bf16 alike.
+SWEEP_BEYOND = {
+    "ffhq": [],
+    "cars": [
+        65,          # the first batch beyond the swept 1..64 (five 16-sample chunks for four mapping slices: tests/test_gpu_large_batch.py)
+        127, 128,    # map 127/128, the only change in 65..128, fp32 and bf16: d.main_1.b conv3x3_mfma<8, 8, 4, 1, 1 -> 2, 2>, d.main_2.a subpixel_mfma<1 -> 2,
+        #              2>, d.main_2.b conv3x3_mfma<16, 16, 4, 1, 1 -> 2, 2> (bf16: conv3x3_bf16_lean NT 1 -> 2); bf16 g.16.conv_1 subpixel_mfma -> subpixel_res.
+        #              128 is the maximum (and the last batch with one round of the style kernels)
+    ],
+    "bedrooms": [
+        65,          # the first batch beyond the swept 1..64 (five 16-sample chunks for four mapping slices)
+        127, 128,    # map 127/128: the same changes as cars at 128 (d.main_1.b, d.main_2.a, d.main_2.b geometry; bf16 g.16.conv_1 -> subpixel_res)
+        129,         # the style kernels' second round (grid.y = 8 rows of 16 samples), a ninth mapping chunk
+        255, 256,    # map 255/256, the only other change in 65..256: d.main_1.b conv3x3_mfma<8, 8, 4, 1, 2, 2> -> <16, 16, 4, 1, 1, 2>, d.main_2.a
+        #              subpixel_mfma<2, 2> -> lean::subpixel_lean (bf16: subpixel_res<.., 1, true>), bf16 d.main_3.a subpixel_res<.., 1, true> -> <.., 2,
+        #              false>.  256 is the maximum
+    ],
+}
+
+
+def sweep_batches(gan):
+    return SWEEP + SWEEP_BEYOND[gan]
+
+
+def test_sweep_lists_reach_each_models_maximum():
+    for gan, top in SWEEP_MAX.items():
+        bs = sweep_batches(gan)
+        assert bs == sorted(set(bs)) and bs[-1] == top
+        if top > 64:
+            assert {b for b in (65, 128, 129, top) if b <= top} <= set(bs)
+
+
 CASES = [(g, p) for g in ("ffhq", "cars", "bedrooms") for p in ("fp32", "bf16")]
 
 
@@ -70,11 +106,13 @@ def _golden_anchors():
 
 
 class Sweep:
-    """One GAN in one mode: the generator reserved for 64, the sweep inputs on the device, and what each sample gives alone."""
+    """One GAN in one mode: the generator reserved for the model's sweep maximum, the sweep inputs on the device, and what each sample
+    gives alone."""
 
     def __init__(self, gan, precision):
         self.gan, self.precision = gan, precision
         self.gen, self.z, self.noise = DM.build(gan, precision)
+        self.max_batch, self.batches = SWEEP_MAX[gan], sweep_batches(gan)
         self._maps = {}
         self._alone = {}
 
@@ -92,7 +130,7 @@ class Sweep:
         if i not in self._alone:
             img, mask = DM.run_path(self.gen, "generate", *self.sl(i, i + 1))
             rgb, feats, _img, logits, _mask = DM.run_path(self.gen, "two_call", *self.sl(i, i + 1))
-            self._alone[i] = (img, mask, rgb, logits, feats if i == 0 or i + 1 in SWEEP else None)
+            self._alone[i] = (img, mask, rgb, logits, feats if i == 0 or i + 1 in self.batches else None)
         return self._alone[i]
 
     def release(self):
@@ -111,22 +149,22 @@ def sweep(request, torch_cuda):
 
 
 def test_sweep_covers_every_dispatch_form(sweep):
-    """Every (layer, kernel) pair that some batch in 1..64 launches is launched by a batch of SWEEP."""
+    """Every (layer, kernel) pair that some batch in 1..SWEEP_MAX[gan] launches is launched by a batch of the model's sweep list."""
     first = {}
-    for b in range(1, SWEEP_MAX_BATCH + 1):
+    for b in range(1, sweep.max_batch + 1):
         for pair in sweep.map(b):
             first.setdefault(pair, b)
-    covered = frozenset().union(*(sweep.map(b) for b in SWEEP))
+    covered = frozenset().union(*(sweep.map(b) for b in sweep.batches))
     missing = sorted((b, layer, kernel) for (layer, kernel), b in first.items() if (layer, kernel) not in covered)
     assert not missing, "%s %s: pairs no SWEEP batch launches:\n%s" % (
         sweep.gan, sweep.precision, "\n".join("  %s  %s  (first at batch %d)" % (layer, kernel, b) for b, layer, kernel in missing))
 
 
 def test_batch_composition_at_every_sweep_batch(sweep):
-    """Each sample of a SWEEP batch == the same sample at batch 1: the fused u8 pair, the two-call rgb and logits, and every feature
-    map of the batch's first and last sample."""
+    """Each sample of a batch of the model's sweep list == the same sample at batch 1: the fused u8 pair, the two-call rgb and logits,
+    and every feature map of the batch's first and last sample."""
     import torch
-    for B in SWEEP:
+    for B in sweep.batches:
         img, mask = DM.run_path(sweep.gen, "generate", *sweep.sl(0, B))
         rgb, feats, _img2, logits, _mask2 = DM.run_path(sweep.gen, "two_call", *sweep.sl(0, B))
         for i in range(B):

@@ -177,3 +177,77 @@ def test_encode_rejects_bad_arguments_before_touching_the_gpu(hip_library):
     for bad in (dict(n=0), dict(H=60), dict(W=8), dict(ri=0), dict(ri=70000), dict(rgb=None), dict(rgb=4097), dict(ws=None),
                 dict(wsb=ws - 1), dict(out=None), dict(ln=None), dict(stride=1), dict(H=65536 + 16)):
         assert call(**bad) == -1, bad
+
+
+# ---- beyond one pass of jpeg_transform_kernel --------------------------------------------------------------------------
+# gsa_jpeg_encode (csrc/gsa_jpeg.hip) caps the transform grid at 8192 workgroups of 4 MCUs (16x16 px); a call with more than
+# TRANSFORM_MCUS_PER_PASS MCUs makes a workgroup walk several groups of 4, reusing its LDS tiles and splitting each MCU index into
+# (image, MCU of the image) again.  The README's disk run, 1024^2 at batch 32, is 131 072 MCUs: four passes.
+TRANSFORM_MCUS_PER_PASS = 8192 * 4
+
+
+def test_the_transform_grid_cap_is_the_one_these_tests_assume():
+    src = open(os.path.join(ROOT, "gan-segmentation_amd", "csrc", "gsa_jpeg.hip")).read()
+    assert "const int tgrid = (total_mcus + 3) / 4 < 8192 ? (total_mcus + 3) / 4 : 8192;" in src
+
+
+def distinct_images(H, W, n, seed):
+    """n pictures (n >= 5) of which no two are equal: images()'s five fixed kinds are not enough for a batch of 32 or 130 -- repeated
+    pictures would hide a wrong image index in a later pass of the transform kernel (image i encoded from the pixels of image j
+    gives the right bytes when the two are the same picture).  One black, one white, and smooth, noise and stripes variants in
+    turn, each from its own seed (the stripes' period, phase and inverted rows come from the seed)."""
+    import torch
+    import torch.nn.functional as F
+    out = []
+    for i in range(n):
+        rng = np.random.default_rng([seed, i])
+        kind = ("black", "white")[i - 3] if i in (3, 4) else ("smooth", "noise", "stripes")[i % 3]
+        if kind == "black":
+            img = np.zeros((H, W, 3), np.uint8)
+        elif kind == "white":
+            img = np.full((H, W, 3), 255, np.uint8)
+        elif kind == "noise":
+            img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        elif kind == "smooth":
+            x = rng.standard_normal((1, 3, max(H // 16, 2), max(W // 16, 2))).astype(np.float32)
+            s = F.interpolate(torch.from_numpy(x), size=(H, W), mode="bicubic", align_corners=False)[0].permute(1, 2, 0).numpy()
+            img = (s * 60 + 128 + rng.standard_normal((H, W, 3), dtype=np.float32) * 5).clip(0, 255).astype(np.uint8)
+        else:
+            period, phase = 2 + int(rng.integers(0, 15)), int(rng.integers(0, 64))
+            col = np.arange(W) + phase
+            img = np.zeros((H, W, 3), np.uint8)
+            img[:, np.arange(W), (col // 3) % 3] = np.where((col // period) % 2, 255, 0).astype(np.uint8)[None, :]
+            flip = rng.random(H) < 0.15                      # inverted rows: which ones is this picture's own
+            img[flip] = 255 - img[flip]
+        out.append(np.ascontiguousarray(img))
+    assert len({a.tobytes() for a in out}) == n, "the pictures of a batch must all differ"
+    return out
+
+
+def test_distinct_images_are_distinct():
+    pics = distinct_images(64, 64, 130, 1)
+    assert len(pics) == 130 and all(p.shape == (64, 64, 3) and p.dtype == np.uint8 for p in pics)
+    assert not pics[3].any() and pics[4].min() == 255
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W,quality,restart,n", [(1024, 1024, 95, 4, 9),      # 36 864 MCUs: a full pass, then one in which 7168 workgroups have no work
+                                                   (1024, 1024, 95, 4, 32),     # 131 072 MCUs: four full passes, the README's run
+                                                   (512, 512, 95, 4, 33),       # 33 792 MCUs: 256 workgroups take a second group
+                                                   (256, 256, 75, 3, 130)])     # 33 280 MCUs of 130 small images; 3 does not divide 256
+def test_hip_encoder_is_byte_identical_beyond_one_pass(torch_cuda, H, W, quality, restart, n):
+    """One call of n pairwise different pictures, byte for byte against the oracle, image by image."""
+    import torch
+    from gan_segmentation_amd.jpeg import JpegEncoder
+    from oracle import jpeg_binding as J
+    assert n * (H // 16) * (W // 16) > TRANSFORM_MCUS_PER_PASS, "the call must take a second pass"
+    pics = distinct_images(H, W, n, 11 + H + n)
+    enc = JpegEncoder(n, H, W, "cuda:0", quality=quality, restart=restart)
+    files = enc.files(torch.from_numpy(np.stack(pics)).cuda())
+    assert len(files) == n
+    wrong = [i for i, (img, f) in enumerate(zip(pics, files)) if f != J.encode(img, quality, restart)]
+    assert not wrong, "%dx%d q%d ri%d n=%d: images %s differ from the oracle's files" % (H, W, quality, restart, n, wrong)
+    from PIL import Image
+    dec = np.asarray(Image.open(io.BytesIO(files[-1])).convert("RGB"))
+    ref = np.asarray(Image.open(io.BytesIO(pillow_bytes(pics[-1], quality, restart))).convert("RGB"))
+    assert np.array_equal(dec, ref)

@@ -128,3 +128,63 @@ def test_dataset_writer_with_gpu_jpeg_and_png(torch_cuda, tmp_path):
             Image.fromarray(img[i], "RGB").save(b, "JPEG", quality=95)
             ref = np.asarray(Image.open(io.BytesIO(b.getvalue())).convert("RGB"))
             assert np.array_equal(np.asarray(Image.open(d / ("img_%06d.jpg" % i)).convert("RGB")), ref), i
+
+
+def distinct_masks(H, W, n, seed):
+    """n class-index masks of which no two are equal: blobs whose position, size and class come from a per-mask seed, a noisy
+    band, and (mask 0) binary noise all over -- the writer's real content is blobs, the noise costs the coder its longest streams."""
+    out = []
+    for i in range(n):
+        rng = np.random.default_rng([seed, i])
+        if i == 0:
+            m = rng.integers(0, 2, (H, W), dtype=np.uint8)
+        else:
+            m = np.zeros((H, W), np.uint8)
+            for _ in range(6):
+                y, x = int(rng.integers(0, H)), int(rng.integers(0, W))
+                m[y:y + int(rng.integers(1, H // 2 + 2)), x:x + int(rng.integers(1, W // 2 + 2))] = rng.integers(0, 8)
+            y = int(rng.integers(0, H))
+            m[y:y + max(H // 64, 1)] = rng.integers(0, 8, m[y:y + max(H // 64, 1)].shape, dtype=np.uint8)
+        out.append(m)
+    assert len({m.tobytes() for m in out}) == n
+    return out
+
+
+@pytest.mark.gpu
+def test_hip_png_decodes_back_at_the_writers_batch(torch_cuda):
+    """1024^2, 32 pairwise different masks in one call (the README's disk run): every file decodes to its own mask."""
+    import torch
+    from gan_segmentation_amd.png import PngEncoder
+    H = W = 1024
+    ms = distinct_masks(H, W, 32, 5)
+    files = PngEncoder(32, H, W, "cuda:0").files(torch.from_numpy(np.stack(ms)).cuda())
+    assert len(files) == 32
+    for i, (m, f) in enumerate(zip(ms, files)):
+        assert np.array_equal(decode(f), m), "mask %d" % i
+
+
+@pytest.mark.gpu
+def test_dataset_writer_at_full_size_in_two_pass_batches(torch_cuda, tmp_path):
+    """DatasetWriter(gpu_jpeg=True, gpu_png=True) at 1024^2 in batches of 16 -- 65 536 MCUs per call, two passes of the JPEG
+    transform kernel (tests/test_jpeg.py) -- and a short last batch of 5: every JPEG decodes to what libjpeg-turbo stores for
+    the same pixels, every PNG holds its mask.  All 37 pictures and masks differ."""
+    import torch
+    from PIL import Image
+    from gan_segmentation_amd.dataset_writer import DatasetWriter
+    from tests.test_jpeg import TRANSFORM_MCUS_PER_PASS, distinct_images
+    R, n, B = 1024, 37, 16
+    assert B * (R // 16) ** 2 > TRANSFORM_MCUS_PER_PASS
+    img = np.stack(distinct_images(R, R, n, 21))
+    mk = np.stack(distinct_masks(R, R, n, 22))
+    d = tmp_path / "out"
+    with DatasetWriter(str(d), workers=4, gpu_jpeg=True, gpu_png=True) as w:
+        for lo in range(0, n, B):
+            w.submit(torch.from_numpy(img[lo:lo + B]).cuda(), torch.from_numpy(mk[lo:lo + B]).cuda(), lo)
+    assert w.written == n
+    assert sorted(os.listdir(d)) == sorted(["img_%06d.jpg" % i for i in range(n)] + ["mask_%06d.png" % i for i in range(n)])
+    for i in range(n):
+        assert np.array_equal(np.asarray(Image.open(d / ("mask_%06d.png" % i))), mk[i]), i
+        b = io.BytesIO()
+        Image.fromarray(img[i], "RGB").save(b, "JPEG", quality=95)
+        ref = np.asarray(Image.open(io.BytesIO(b.getvalue())).convert("RGB"))
+        assert np.array_equal(np.asarray(Image.open(d / ("img_%06d.jpg" % i)).convert("RGB")), ref), i
