@@ -14,6 +14,11 @@
 //   jpeg_offsets_kernel    per image: exclusive scan of the segment lengths, EOI marker, total length
 //   jpeg_gather_kernel     one wave per segment: scratch -> its final position in the image's scan
 // Bit-exact contract: oracle/c/jpeg_oracle.c (itself byte-identical to libjpeg-turbo via Pillow).
+// The round trip of the training stream (include/gsa_jpeg_roundtrip.h) shares the transform's front:
+//   jpeg_roundtrip_mcu_kernel    the same forward work, then dequantisation and libjpeg's inverse DCT without leaving the wave:
+//                          decoded Y / Cb / Cr sample planes into the workspace        (3 B/px read, 1.5 B/px written)
+//   jpeg_roundtrip_merge_kernel  triangle upsampling of the chroma planes + YCbCr -> RGB  (1.5 B/px read, 3 B/px written)
+// Bit-exact contract: tests/test_jpeg_roundtrip_host.py rule_roundtrip (pinned against libjpeg-turbo's decoder via Pillow).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -21,6 +26,7 @@
 
 #include "../../include/gsa.h"
 #include "../../include/gsa_jpeg.h"
+#include "../../include/gsa_jpeg_roundtrip.h"
 
 namespace {
 
@@ -125,6 +131,61 @@ __device__ __forceinline__ void dct8(int (&v)[8]) {
     v[1] = descale(a7 + z1 + z4, SH);
 }
 
+// Quantisation of one coefficient of the 8x-scaled DCT by dv = step << 3: round half away from zero.
+__device__ __forceinline__ int quantise(int v, unsigned dv) {
+    const unsigned a = (unsigned)(v < 0 ? -v : v);
+    const int qv = (int)((a + (dv >> 1)) / dv);
+    return v < 0 ? -qv : qv;
+}
+
+// The front of one wave's 16x16-px MCU (wave-private LDS tiles `raw`, `comp`; called by all four waves of the block alike):
+// 16-byte loads of the RGB rows, colour conversion, 2x2 chroma box, and the ROW pass of the DCT.  On return comp[blk] holds the
+// six row-transformed 8x8 blocks (Y00 Y01 Y10 Y11 Cb Cr, natural order) behind a barrier.
+__device__ __forceinline__ void mcu_rows(const uint8_t* __restrict__ rgb, int H, int W, int img, int my, int mx, bool active,
+                                         int lane, uint8_t* raw, int (*comp)[64]) {
+    if (active && lane < 48) {   // 16 rows x 48 bytes, 16 bytes per lane
+        const int row = lane / 3, part = lane - row * 3;
+        const uint8_t* src = rgb + ((size_t)((size_t)img * H + my * 16 + row) * W + mx * 16) * 3 + part * 16;
+        *reinterpret_cast<uint4*>(&raw[row * 48 + part * 16]) = *reinterpret_cast<const uint4*>(src);
+    }
+    __syncthreads();
+    if (active) {   // a lane converts 4 neighbouring pixels of one row
+        const int y = lane >> 2, x0 = (lane & 3) * 4;
+        const uint8_t* px = &raw[(y * 16 + x0) * 3];
+        int cb[4], cr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = px[3 * j], g = px[3 * j + 1], b = px[3 * j + 2];
+            // 16-bit fixed point: Y = .299R+.587G+.114B; Cb = -.16874R-.33126G+.5B+128; Cr = .5R-.41869G-.08131B+128
+            const int Y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+            cb[j] = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+            cr[j] = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+            comp[(y >> 3) * 2 + (x0 >> 3)][(y & 7) * 8 + ((x0 + j) & 7)] = Y - 128;
+        }
+        // 2x2 box filter: horizontal pairs here, the row below sits 4 lanes up; rounding bias alternates 1, 2
+        const int b01 = cb[0] + cb[1], b23 = cb[2] + cb[3], r01 = cr[0] + cr[1], r23 = cr[2] + cr[3];
+        const int ob01 = __shfl_down(b01, 4), ob23 = __shfl_down(b23, 4), or01 = __shfl_down(r01, 4), or23 = __shfl_down(r23, 4);
+        if (!(y & 1)) {
+            const int o = (y >> 1) * 8 + (lane & 3) * 2;
+            comp[4][o] = ((b01 + ob01 + 1) >> 2) - 128;
+            comp[4][o + 1] = ((b23 + ob23 + 2) >> 2) - 128;
+            comp[5][o] = ((r01 + or01 + 1) >> 2) - 128;
+            comp[5][o + 1] = ((r23 + or23 + 2) >> 2) - 128;
+        }
+    }
+    __syncthreads();
+    const int blk = lane >> 3, rc = lane & 7;
+    if (active && lane < 48) {   // rows
+        int v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = comp[blk][rc * 8 + i];
+        dct8<0>(v);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) comp[blk][rc * 8 + i] = v[i];
+    }
+    __syncthreads();
+}
+
 // coef: [image][MCU][6 blocks: Y00 Y01 Y10 Y11 Cb Cr][64 zigzag] int16
 __global__ __launch_bounds__(256) void jpeg_transform_kernel(const uint8_t* __restrict__ rgb, int H, int W, int mcus_x,
                                                              int mcus_per_img, int total_mcus, QDiv q,
@@ -139,47 +200,8 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(const uint8_t* __re
         const int img = active ? m / mcus_per_img : 0;
         const int mi = active ? m - img * mcus_per_img : 0;
         const int my = mi / mcus_x, mx = mi - my * mcus_x;
-        if (active && lane < 48) {   // 16 rows x 48 bytes, 16 bytes per lane
-            const int row = lane / 3, part = lane - row * 3;
-            const uint8_t* src = rgb + ((size_t)((size_t)img * H + my * 16 + row) * W + mx * 16) * 3 + part * 16;
-            *reinterpret_cast<uint4*>(&raw[wave][row * 48 + part * 16]) = *reinterpret_cast<const uint4*>(src);
-        }
-        __syncthreads();
-        if (active) {   // a lane converts 4 neighbouring pixels of one row
-            const int y = lane >> 2, x0 = (lane & 3) * 4;
-            const uint8_t* px = &raw[wave][(y * 16 + x0) * 3];
-            int cb[4], cr[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = px[3 * j], g = px[3 * j + 1], b = px[3 * j + 2];
-                // 16-bit fixed point: Y = .299R+.587G+.114B; Cb = -.16874R-.33126G+.5B+128; Cr = .5R-.41869G-.08131B+128
-                const int Y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
-                cb[j] = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
-                cr[j] = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
-                comp[wave][(y >> 3) * 2 + (x0 >> 3)][(y & 7) * 8 + ((x0 + j) & 7)] = Y - 128;
-            }
-            // 2x2 box filter: horizontal pairs here, the row below sits 4 lanes up; rounding bias alternates 1, 2
-            const int b01 = cb[0] + cb[1], b23 = cb[2] + cb[3], r01 = cr[0] + cr[1], r23 = cr[2] + cr[3];
-            const int ob01 = __shfl_down(b01, 4), ob23 = __shfl_down(b23, 4), or01 = __shfl_down(r01, 4), or23 = __shfl_down(r23, 4);
-            if (!(y & 1)) {
-                const int o = (y >> 1) * 8 + (lane & 3) * 2;
-                comp[wave][4][o] = ((b01 + ob01 + 1) >> 2) - 128;
-                comp[wave][4][o + 1] = ((b23 + ob23 + 2) >> 2) - 128;
-                comp[wave][5][o] = ((r01 + or01 + 1) >> 2) - 128;
-                comp[wave][5][o + 1] = ((r23 + or23 + 2) >> 2) - 128;
-            }
-        }
-        __syncthreads();
+        mcu_rows(rgb, H, W, img, my, mx, active, lane, raw[wave], comp[wave]);
         const int blk = lane >> 3, rc = lane & 7;
-        if (active && lane < 48) {   // rows
-            int v[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = comp[wave][blk][rc * 8 + i];
-            dct8<0>(v);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) comp[wave][blk][rc * 8 + i] = v[i];
-        }
-        __syncthreads();
         if (active && lane < 48) {   // columns, quantisation (round half away from zero), zigzag
             int v[8];
 #pragma unroll
@@ -189,15 +211,144 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(const uint8_t* __re
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int nat = i * 8 + rc;
-                const unsigned dv = d[nat];
-                const unsigned a = (unsigned)(v[i] < 0 ? -v[i] : v[i]);
-                const int qv = (int)((a + (dv >> 1)) / dv);
-                zz[wave][blk * 64 + kZigInvDev.p[nat]] = (int16_t)(v[i] < 0 ? -qv : qv);
+                zz[wave][blk * 64 + kZigInvDev.p[nat]] = (int16_t)quantise(v[i], d[nat]);
             }
         }
         __syncthreads();
         if (active && lane < 48)
             reinterpret_cast<uint4*>(coef + (size_t)m * 384)[lane] = reinterpret_cast<const uint4*>(&zz[wave][0])[lane];
+    }
+}
+
+// ---- the round trip (include/gsa_jpeg_roundtrip.h): the pixels a libjpeg decoder rebuilds from the coefficients above ------------
+// One 8-point pass of libjpeg's jidctint (CONST_BITS 13, PASS1_BITS 2): N = 11 in the column pass, which comes first, N = 18 in
+// the row pass.  int32 holds every intermediate: a dequantised coefficient is a true coefficient (|.| <= 1024) plus at most half a
+// quantiser step (<= 128); the column pass returns 4 x a 1-D transform of the samples (<= 4096) plus the transformed quantisation
+// error (<= 5462), below 9558; the largest intermediate of a pass is below 137832 x its largest input (the odd-part term of d[3])
+// and an output adds at most 31520 x from the even part: below 1.62e9.
+template <int N>
+__device__ __forceinline__ void idct8(int (&d)[8]) {
+    int z1 = (d[2] + d[6]) * 4433;
+    const int t2 = z1 - d[6] * 15137, t3 = z1 + d[2] * 6270;
+    const int t0 = (d[0] + d[4]) * 8192, t1 = (d[0] - d[4]) * 8192;
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    int a0 = d[7], a1 = d[5], a2 = d[3], a3 = d[1];
+    z1 = a0 + a3;
+    int z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+    const int z5 = (z3 + z4) * 9633;
+    a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299;
+    z1 *= -7373; z2 *= -20995;
+    z3 = z3 * -16069 + z5;
+    z4 = z4 * -3196 + z5;
+    a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4;
+    d[0] = descale(t10 + a3, N); d[7] = descale(t10 - a3, N);
+    d[1] = descale(t11 + a2, N); d[6] = descale(t11 - a2, N);
+    d[2] = descale(t12 + a1, N); d[5] = descale(t12 - a1, N);
+    d[3] = descale(t13 + a0, N); d[4] = descale(t13 - a0, N);
+}
+
+__device__ __forceinline__ unsigned clamp255(int v) { return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+// Stage 1, one wave per MCU as jpeg_transform_kernel: the same front and column pass, then -- the coefficients never leave the
+// lane that quantised them -- dequantisation and the IDCT's column pass in registers, its row pass through LDS, and 8-byte stores
+// of the decoded sample rows: Y at full size (n,H,W), Cb and Cr at half size (n,H/2,W/2).
+__global__ __launch_bounds__(256) void jpeg_roundtrip_mcu_kernel(const uint8_t* __restrict__ rgb, int H, int W, int mcus_x,
+                                                                 int mcus_per_img, int total_mcus, QDiv q,
+                                                                 uint8_t* __restrict__ yp, uint8_t* __restrict__ cbp,
+                                                                 uint8_t* __restrict__ crp) {
+    __shared__ __attribute__((aligned(16))) uint8_t raw[4][768];
+    __shared__ int comp[4][6][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int base = blockIdx.x * 4; base < total_mcus; base += gridDim.x * 4) {   // trip count uniform over the block
+        const int m = base + wave;
+        const bool active = m < total_mcus;
+        const int img = active ? m / mcus_per_img : 0;
+        const int mi = active ? m - img * mcus_per_img : 0;
+        const int my = mi / mcus_x, mx = mi - my * mcus_x;
+        mcu_rows(rgb, H, W, img, my, mx, active, lane, raw[wave], comp[wave]);
+        const int blk = lane >> 3, rc = lane & 7;
+        if (active && lane < 48) {   // column rc: forward pass, quantise, dequantise (dv >> 3 is the plain step), inverse pass
+            int v[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = comp[wave][blk][i * 8 + rc];
+            dct8<1>(v);
+            const uint16_t* d = q.d[blk < 4 ? 0 : 1];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const unsigned dv = d[i * 8 + rc];
+                v[i] = quantise(v[i], dv) * (int)(dv >> 3);
+            }
+            idct8<11>(v);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) comp[wave][blk][i * 8 + rc] = v[i];
+        }
+        __syncthreads();
+        if (active && lane < 48) {   // row rc of block blk: inverse pass, level shift, clamp, one 8-byte store
+            int v[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = comp[wave][blk][rc * 8 + i];
+            idct8<18>(v);
+            uint2 o;
+            o.x = clamp255(v[0] + 128) | (clamp255(v[1] + 128) << 8) | (clamp255(v[2] + 128) << 16) | (clamp255(v[3] + 128) << 24);
+            o.y = clamp255(v[4] + 128) | (clamp255(v[5] + 128) << 8) | (clamp255(v[6] + 128) << 16) | (clamp255(v[7] + 128) << 24);
+            uint8_t* dst;
+            if (blk < 4) dst = yp + ((size_t)img * H + my * 16 + (blk >> 1) * 8 + rc) * W + mx * 16 + (blk & 1) * 8;
+            else dst = (blk == 4 ? cbp : crp) + ((size_t)img * (H >> 1) + my * 8 + rc) * (W >> 1) + mx * 8;
+            *reinterpret_cast<uint2*>(dst) = o;
+        }
+        // the next trip's first write to comp comes behind the barrier that follows its load of raw
+    }
+}
+
+// Stage 2, one thread per 8 neighbouring pixels of an output row: libjpeg-turbo's h2v2 "fancy" (triangle) upsampling of the
+// two chroma planes -- near row 3 : far row 1, then near column 3 : far column 1, rows and columns replicated at the edges of
+// THE IMAGE -- and YCbCr -> RGB in 16-bit fixed point.  8 Y bytes and per plane and row 4 aligned + 2 edge bytes in, 24 bytes out.
+__global__ __launch_bounds__(256) void jpeg_roundtrip_merge_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cbp,
+                                                                   const uint8_t* __restrict__ crp, int H, int W, long long total,
+                                                                   uint8_t* __restrict__ out) {
+    const int W8 = W >> 3, H2 = H >> 1, W2 = W >> 1;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long line = t / W8;                  // image * H + row
+        const int xg = (int)(t - line * W8);
+        const int img = (int)(line / H), y = (int)(line - (long long)img * H);
+        const int r = y >> 1, far = (y & 1) ? min(r + 1, H2 - 1) : max(r - 1, 0);
+        const int c0 = xg * 4, cl = max(c0 - 1, 0), cr_ = min(c0 + 4, W2 - 1);
+        const size_t nearoff = ((size_t)img * H2 + r) * W2, faroff = ((size_t)img * H2 + far) * W2;
+        const uint2 yy = *reinterpret_cast<const uint2*>(yp + (size_t)line * W + xg * 8);
+        int up[2][8];                                    // the upsampled Cb, Cr of the 8 pixels
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const uint8_t* pl = p ? crp : cbp;
+            const unsigned n4 = *reinterpret_cast<const unsigned*>(pl + nearoff + c0);
+            const unsigned f4 = *reinterpret_cast<const unsigned*>(pl + faroff + c0);
+            int s[6];                                    // 3 near + far of the columns c0-1 .. c0+4
+            s[0] = 3 * pl[nearoff + cl] + pl[faroff + cl];
+            s[5] = 3 * pl[nearoff + cr_] + pl[faroff + cr_];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[1 + j] = 3 * (int)((n4 >> (8 * j)) & 255u) + (int)((f4 >> (8 * j)) & 255u);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                up[p][2 * j] = (3 * s[1 + j] + s[j] + 8) >> 4;
+                up[p][2 * j + 1] = (3 * s[1 + j] + s[2 + j] + 7) >> 4;
+            }
+        }
+        unsigned char px[24];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int Y = (int)(((k < 4 ? yy.x : yy.y) >> (8 * (k & 3))) & 255u);
+            const int cb = up[0][k] - 128, cr = up[1][k] - 128;
+            px[3 * k] = (unsigned char)clamp255(Y + ((91881 * cr + 32768) >> 16));
+            px[3 * k + 1] = (unsigned char)clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+            px[3 * k + 2] = (unsigned char)clamp255(Y + ((116130 * cb + 32768) >> 16));
+        }
+        unsigned w[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+            w[k] = (unsigned)px[4 * k] | ((unsigned)px[4 * k + 1] << 8) | ((unsigned)px[4 * k + 2] << 16) | ((unsigned)px[4 * k + 3] << 24);
+        uint2* dst = reinterpret_cast<uint2*>(out + ((size_t)line * W + xg * 8) * 3);
+        dst[0] = make_uint2(w[0], w[1]);
+        dst[1] = make_uint2(w[2], w[3]);
+        dst[2] = make_uint2(w[4], w[5]);
     }
 }
 
@@ -568,6 +719,41 @@ int gsa_jpeg_encode(void* stream, int32_t n, int32_t H, int32_t W, const uint8_t
                        (long long)out_stride);
     hipLaunchKernelGGL(jpeg_gather_kernel, dim3((total_segs + 3) / 4), dim3(256), 0, s, scratch, seglen, segoff,
                        g.segs_per_img, total_segs, g.segcap, out, (long long)out_stride);
+    return hipGetLastError() == hipSuccess ? GSA_OK : GSA_ERR_HIP;
+}
+
+int64_t gsa_jpeg_roundtrip_workspace_bytes(int32_t n, int32_t H, int32_t W) {
+    if (n < 0 || H < 16 || W < 16 || H % 16 || W % 16 || H > 65535 || W > 65535) return GSA_ERR_INVALID;
+    return (int64_t)n * H * W / 2 * 3;
+}
+
+int gsa_jpeg_roundtrip(void* stream, int32_t n, int32_t H, int32_t W, const uint8_t* rgb, int32_t quality, void* workspace,
+                       int64_t workspace_bytes, uint8_t* out) {
+    const int64_t need = gsa_jpeg_roundtrip_workspace_bytes(n, H, W);
+    if (need < 0 || quality < 1 || quality > 100) return GSA_ERR_INVALID;
+    if (!rgb || !workspace || !out || out == rgb || workspace_bytes < need) return GSA_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(rgb) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
+        return GSA_ERR_INVALID;
+    const int mcus_per_img = (H / 16) * (W / 16);
+    if ((int64_t)n * mcus_per_img > 0x7fffffffll / 4) return GSA_ERR_INVALID;
+    if (n == 0) return GSA_OK;
+    uint8_t ql[64], qc[64];
+    quant_table(kBaseLuma, quality, ql);
+    quant_table(kBaseChroma, quality, qc);
+    QDiv q;
+    for (int i = 0; i < 64; ++i) { q.d[0][i] = (uint16_t)(ql[i] << 3); q.d[1][i] = (uint16_t)(qc[i] << 3); }
+    const size_t plane = (size_t)n * H * W;
+    uint8_t* yp = static_cast<uint8_t*>(workspace);
+    uint8_t* cbp = yp + plane;
+    uint8_t* crp = cbp + plane / 4;
+    const int total_mcus = n * mcus_per_img;
+    // both grids are capped at what covers 8192 MCUs (2 Mpx) in one pass: 32 waves for each of the 256 CUs in stage 1
+    const int rgrid = (total_mcus + 3) / 4 < 2048 ? (total_mcus + 3) / 4 : 2048;
+    hipLaunchKernelGGL(jpeg_roundtrip_mcu_kernel, dim3(rgrid), dim3(256), 0, (hipStream_t)stream, rgb, H, W, W / 16, mcus_per_img,
+                       total_mcus, q, yp, cbp, crp);
+    const long long groups = (long long)(plane / 8);                 // 8 pixels of a row per thread
+    const int mgrid = (groups + 255) / 256 < 1024 ? (int)((groups + 255) / 256) : 1024;
+    hipLaunchKernelGGL(jpeg_roundtrip_merge_kernel, dim3(mgrid), dim3(256), 0, (hipStream_t)stream, yp, cbp, crp, H, W, groups, out);
     return hipGetLastError() == hipSuccess ? GSA_OK : GSA_ERR_HIP;
 }
 

@@ -3,7 +3,10 @@ half of the dataset writer (reference main.py:100-101 ``
 
 ``JpegEncoder(n, H, W)`` owns the device workspace and output buffers for batches of up to ``n`` images;
 ``encode(img)`` enqueues the kernels on the current stream of ``img`` and returns device tensors
-``(scan (n, stride) u8, lengths (n,) i32)``; a file is ``encoder.header + scan[i, :lengths[i]]``.  No CPU fallback."""
+``(scan (n, stride) u8, lengths (n,) i32)``; a file is ``encoder.header + scan[i, :lengths[i]]``.  No CPU fallback.
+
+``roundtrip(img)`` (include/gsa_jpeg_roundtrip.h) returns the pixels a reader of those files would decode,
+bit for bit, without writing them: what ``ImageGenerator.training_batches(jpeg_quality=...)`` feeds the augmentation."""
 import ctypes
 
 import torch
@@ -99,3 +102,80 @@ class JpegEncoder:
             ln = lengths.cpu().numpy()
         host = scan.cpu().numpy()
         return [self.header + host[i, :ln[i]].tobytes() for i in range(len(ln))]
+
+
+# -- the round trip (include/gsa_jpeg_roundtrip.h) -------------------------------------------------------------------------------
+_ROUNDTRIP_FUNCS = None
+_ROUNDTRIP_WORKSPACES = {}       # (device index, stream, bytes) -> u8 tensor; a handful of sizes per process
+_ROUNDTRIP_WORKSPACES_MAX = 8
+
+
+def _roundtrip_api():
+    global _ROUNDTRIP_FUNCS
+    if _ROUNDTRIP_FUNCS is None:
+        lib = _lib.load_library().lib
+        c = ctypes
+        vp, i32, i64 = c.c_void_p, c.c_int32, c.c_int64
+        sig = {
+            "gsa_jpeg_roundtrip_workspace_bytes": (i64, [i32, i32, i32]),
+            "gsa_jpeg_roundtrip": (c.c_int, [vp, i32, i32, i32, vp, i32, vp, i64, vp]),
+        }
+        _ROUNDTRIP_FUNCS = {}
+        for name, (res, args) in sig.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+            _ROUNDTRIP_FUNCS[name] = fn
+    return _ROUNDTRIP_FUNCS
+
+
+def check_quality(quality, what="quality"):
+    """``quality`` as an int in 1..100 (the encoder's range); ValueError otherwise."""
+    import numbers
+    if isinstance(quality, bool) or not isinstance(quality, numbers.Integral) or not 1 <= int(quality) <= 100:
+        raise ValueError("%s must be an int in 1..100, got %r" % (what, quality))
+    return int(quality)
+
+
+def check_roundtrip_shape(H, W, channels):
+    """The shapes the round trip takes (4:2:0 colour files of whole 16x16-px MCUs); ValueError otherwise."""
+    if int(channels) != 3:
+        raise ValueError("the JPEG round trip takes three image channels, got %d" % channels)
+    if int(H) < 16 or int(W) < 16 or int(H) % 16 or int(W) % 16 or int(H) > 65535 or int(W) > 65535:
+        raise ValueError("the JPEG round trip takes images whose sides are a multiple of 16 px (16..65535), got %dx%d" % (H, W))
+
+
+def roundtrip(img, quality=DEFAULT_QUALITY, out=None):
+    """img (n, H, W, 3) contiguous uint8 CUDA tensor, H and W multiples of 16 -> a tensor of the same shape (new, or ``out``, which
+    must not be ``img``): the pixels a libjpeg decoder returns for the quality-``quality`` 4:2:0 file of every image, bit for bit what
+    a reader of ``JpegEncoder``'s files sees.  Enqueued on the current stream of ``img``'s device; the workspace (1.5 bytes per
+    pixel) is cached per device, stream and size.  No CPU fallback."""
+    quality = check_quality(quality)
+    if not isinstance(img, torch.Tensor) or img.dim() != 4 or not img.is_cuda or img.dtype != torch.uint8 or not img.is_contiguous():
+        raise ValueError("roundtrip takes a contiguous uint8 CUDA tensor (n, H, W, 3)")
+    n, H, W, C = img.shape
+    check_roundtrip_shape(H, W, C)
+    dev = img.device
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(img.shape) or out.dtype != torch.uint8 or out.device != dev
+                or not out.is_contiguous() or (n and out.data_ptr() == img.data_ptr())):
+            raise ValueError("out must be another contiguous uint8 tensor %s on %s" % (tuple(img.shape), dev))
+    api = _roundtrip_api()
+    with torch.cuda.device(dev):        # the C ABI is stateless: the kernels go to the calling thread's current device
+        if out is None:
+            out = torch.empty_like(img)
+        if n == 0:
+            return out
+        need = api["gsa_jpeg_roundtrip_workspace_bytes"](n, H, W)
+        if need < 0:
+            raise _lib.GsaError("gsa_jpeg_roundtrip_workspace_bytes failed (%d)" % need)
+        stream = current_stream_ptr(dev)
+        key = (dev.index, stream, need)
+        ws = _ROUNDTRIP_WORKSPACES.get(key)
+        if ws is None:
+            if len(_ROUNDTRIP_WORKSPACES) >= _ROUNDTRIP_WORKSPACES_MAX:
+                _ROUNDTRIP_WORKSPACES.pop(next(iter(_ROUNDTRIP_WORKSPACES)))
+            ws = _ROUNDTRIP_WORKSPACES[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        rc = api["gsa_jpeg_roundtrip"](stream, n, H, W, img.data_ptr(), quality, ws.data_ptr(), ws.numel(), out.data_ptr())
+    if rc != 0:
+        raise _lib.GsaError("gsa_jpeg_roundtrip failed (%d)" % rc)
+    return out
