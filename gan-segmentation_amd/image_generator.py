@@ -117,12 +117,13 @@ class ImageGenerator:
 
     @staticmethod
     def check_output_downscale(f, max_res_log2):
-        """The output downscale factor f as an int: 1, 2, 4 or 8, leaving at least 16 px of the 2**max_res_log2 output
-        (ValueError otherwise)."""
+        """The output downscale factor f as an int: 1, 2, 4 or 8, a real downscale (f > 1) leaving at least 16 px of the
+        2**max_res_log2 output (ValueError otherwise).  Factor 1 asks for nothing: a generator of 4 or 8 px, which the library accepts
+        without a decoder, passes."""
         if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or int(f) not in (1, 2, 4, 8):
             raise ValueError("output_downscale must be 1, 2, 4 or 8, got %r" % (f,))
         f = int(f)
-        if (2 ** max_res_log2) // f < 16:
+        if f > 1 and (2 ** max_res_log2) // f < 16:
             raise ValueError("output_downscale %d leaves %d px of the %d px output (at least 16 needed)"
                              % (f, (2 ** max_res_log2) // f, 2 ** max_res_log2))
         return f

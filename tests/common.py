@@ -50,6 +50,81 @@ def odd_setup(batch, live_mapping=False):
     return gcfg, gp, dcfg, dp, z, noise
 
 
+# Output configurations the library accepts beside the trained models': generator_config keywords per name.  Channels per level:
+# S4a [64], S4b [512], S8a [64, 64], S8b [512, 512] (generator only: a decoder needs 16 px), S16a [64, 32, 16], S16b [64] x 3,
+# S16c [512] x 3, S32a [64, 64, 32, 16], S32b [64] x 4, S32c [512] x 4, M64 [64, 64, 64, 64, 32], M128 = reduced_setup(7)'s
+# [64, 64, 64, 64, 32, 16], ODD = odd_setup's 48 everywhere, D2 [64 x 5, 16] (a 4:1 step between the last two levels).
+# S4d [16] and S8d [16, 16] put the one-pixel-per-thread toRGB (16 channels) on a partial block; M64d [64, 64, 64, 32, 16] is the
+# smallest output whose last level has 16 channels and takes the Winograd form (64 px: the fused cvt+toRGB kernel's minimum).
+OUTPUT_FORMS = {
+    "S4a": dict(max_res_log2=2, fmap_base=1024, fmap_max=64), "S4b": dict(max_res_log2=2, fmap_base=8192, fmap_max=512),
+    "S4d": dict(max_res_log2=2, fmap_base=1024, fmap_max=16),
+    "S8a": dict(max_res_log2=3, fmap_base=1024, fmap_max=64), "S8b": dict(max_res_log2=3, fmap_base=8192, fmap_max=512),
+    "S8d": dict(max_res_log2=3, fmap_base=1024, fmap_max=16),
+    "S16a": dict(max_res_log2=4, fmap_base=128, fmap_max=64), "S16b": dict(max_res_log2=4, fmap_base=1024, fmap_max=64),
+    "S16c": dict(max_res_log2=4, fmap_base=8192, fmap_max=512),
+    "S32a": dict(max_res_log2=5, fmap_base=256, fmap_max=64), "S32b": dict(max_res_log2=5, fmap_base=1024, fmap_max=64),
+    "S32c": dict(max_res_log2=5, fmap_base=8192, fmap_max=512),
+    "M64": dict(max_res_log2=6, fmap_base=1024, fmap_max=64), "M64d": dict(max_res_log2=6, fmap_base=512, fmap_max=64),
+    "M128": dict(max_res_log2=7, fmap_base=1024, fmap_max=64),
+    "ODD": dict(max_res_log2=7, fmap_base=3072, fmap_max=48),
+    "D2": dict(max_res_log2=7, fmap_base=65536, fmap_max=64, fmap_decay=2.0),
+}
+
+
+def colours_for(k):
+    """The colour count paired with class count k: 1, 2, 4, 3, 1, 2, 4, 3 for k = 1..8."""
+    return (1, 2, 4, 3)[(k - 1) % 4]
+
+
+def form_setup(name, batch, channels=3, classes=2, live_mapping=True, decoder_seed=None, last_feature=None, **overrides):
+    """(gcfg, gp, dcfg, dp, z, noise) of OUTPUT_FORMS[name] with `channels` colours and a `classes`-class decoder (None below 16 px):
+    the synthetic weights of reduced_setup / odd_setup (generator seed 2, ODD 11; decoder seed 3, ODD 12; loaded norm parameters),
+    the mapping layers of lively() unless live_mapping=False.  last_feature: the decoder's width at the output resolution (16 as in the
+    1024 px decoder, instead of 32).  overrides: further generator_config keys (use_wscale=False)."""
+    odd = name == "ODD"
+    gcfg = W.generator_config(channels=channels, **dict(OUTPUT_FORMS[name], **overrides))
+    gp = W.synthetic_generator_params(gcfg, seed=11 if odd else 2, trivial_norm=False)
+    if live_mapping:
+        gp = lively(gp)
+        if not gcfg["use_wscale"]:      # no std factor at run time: a trained file holds it inside the weights (unscaled, w overflows)
+            for i in range(8):
+                gp["mp_dense_%d_weight" % i] = gp["mp_dense_%d_weight" % i] * W.formula_constants(gcfg)["mp_dense_%d_std" % i]
+    dcfg = dp = None
+    mrl = gcfg["max_res_log2"]
+    if mrl >= 4:
+        dcfg = W.decoder_config(mrl, num_classes=classes, in_channels=W.generator_channels(gcfg))
+        if odd:
+            dcfg["features"] = [48, 32, 48, 80, 16, 48, classes]
+        if last_feature is not None:
+            dcfg["features"][-2] = last_feature
+        dp = W.synthetic_decoder_params(dcfg, seed=decoder_seed if decoder_seed is not None else (12 if odd else 3))
+    z, noise = W.synthetic_inputs(gcfg, batch)
+    return gcfg, gp, dcfg, dp, z, noise
+
+
+def sliced_model(gcfg, gp, dcfg, dp, channels, classes):
+    """The model that keeps the first `channels` toRGB rows and the first `classes` rows of the decoder's final conv of
+    (gcfg, gp, dcfg, dp): every output row is a chain of its own, so its rgb / image / logits are the slices of the full model's and
+    its mask is the first maximum over the sliced logits."""
+    R = 2 ** gcfg["max_res_log2"]
+    last = len(dcfg["in_channels"]) - 1
+    g = dict(gcfg, channels=channels)
+    d = dict(dcfg, num_classes=classes, features=list(dcfg["features"][:-1]) + [classes])
+    p, q = dict(gp), dict(dp)
+    for key in ("%d_conv_to_rgb_weight" % R, "%d_conv_to_rgb_bias" % R):
+        p[key] = np.ascontiguousarray(gp[key][:channels])
+    for key in ("main_block_%d.0.weight" % last, "main_block_%d.0.bias" % last):
+        q[key] = np.ascontiguousarray(dp[key][:classes])
+    return g, p, d, q
+
+
+def unsaturated_colours(img):
+    """Colours of the u8 image (N, R, R, nc) that hold a byte strictly between 0 and 255."""
+    img = np.asarray(img)
+    return [c for c in range(img.shape[-1]) if ((img[..., c] > 0) & (img[..., c] < 255)).any()]
+
+
 def w_spread(w):
     """max |w_i - w_0| over the samples of w (N, latent): how much the mapping output depends on z."""
     w = np.asarray(w, np.float64)

@@ -73,6 +73,17 @@ def test_output_downscale_accepts(f):
     assert type(ImageGenerator.check_output_downscale(f, 7)) is int
 
 
+@pytest.mark.parametrize("max_res_log2", [2, 3, 4])
+def test_factor_one_passes_at_every_size(max_res_log2):
+    """No downscale, no 16 px floor: ImageGenerator.from_params builds the 4 and 8 px generators the library accepts
+    (tests/test_gpu_output_forms.py runs them)."""
+    from gan_segmentation_amd.image_generator import ImageGenerator
+    assert ImageGenerator.check_output_downscale(1, max_res_log2) == 1
+    if max_res_log2 < 5:
+        with pytest.raises(ValueError, match="output_downscale"):
+            ImageGenerator.check_output_downscale(2, max_res_log2)
+
+
 @pytest.mark.parametrize("f,max_res_log2", [(3, 10), (16, 10), (0, 10), (-2, 10), (2.0, 10), ("2", 10), (True, 10), (None, 10),
                                             (8, 6), (4, 5), (2, 4)])
 def test_output_downscale_rejects(f, max_res_log2):
