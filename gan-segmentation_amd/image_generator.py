@@ -23,6 +23,10 @@ include/gsa.h and DESIGN.md section 11).  ``get_images`` and everything that fee
 
 ``training_batches`` is the consumer side without files: an iterator of augmented, normalised NCHW batches with their labels, made
 on the GPU from ``generate_indexed`` pairs by the plan and the kernel of ``augment``.
+
+``mask_morph=True`` (fixed at construction, off by default) cleans the mask of every fused call -- the same calls as above, and
+therefore ``training_batches`` -- with ``mask_ops.morph_mask``, the 5x5 close + open of reference utils.morph_mask (DESIGN.md
+section 14): the mask returned is the rule applied to what the same call returns without the option, the image is untouched.
 """
 import os
 
@@ -31,6 +35,7 @@ import torch
 
 from . import augment as _augment
 from . import jpeg as _jpeg
+from . import mask_ops as _mask_ops
 from . import style_mix as _style_mix
 from . import weights as _weights
 from ._runtime import current_stream_ptr, split_sizes, to_device_f32
@@ -45,12 +50,14 @@ _GRAPH_CAPTURES_MAX = 16
 class ImageGenerator:
     style_mix_prob = 0.0
     output_downscale = 1
+    mask_morph = False
 
     def __init__(self, gpu_ids, gan_dir, gan="ffhq", batch_size=4, return_latents=False, seed=0, precision="fp32",
-                 truncation_psi=None, style_mix_prob=0.0, output_downscale=1):
+                 truncation_psi=None, style_mix_prob=0.0, output_downscale=1, mask_morph=False):
         max_res_log2_dict = _weights.GAN_MAX_RES_LOG2
         self.max_res_log2 = max_res_log2_dict[gan]
         self.output_downscale = self.check_output_downscale(output_downscale, self.max_res_log2)
+        self.mask_morph = self.check_mask_morph(mask_morph)
         self.latent_size = 512
         self.return_latents = return_latents
         self.batch_size = batch_size
@@ -80,11 +87,13 @@ class ImageGenerator:
 
     @classmethod
     def from_params(cls, gcfg, gparams, dcfg=None, dparams=None, gpu_ids=(0,), batch_size=4,
-                    return_latents=False, seed=0, precision="fp32", truncation_psi=None, style_mix_prob=0.0, output_downscale=1):
+                    return_latents=False, seed=0, precision="fp32", truncation_psi=None, style_mix_prob=0.0, output_downscale=1,
+                    mask_morph=False):
         """Build from in-memory weights (tests, benchmarks: no pretrained files exist here)."""
         self = cls.__new__(cls)
         self.max_res_log2 = gcfg["max_res_log2"]
         self.output_downscale = cls.check_output_downscale(output_downscale, self.max_res_log2)
+        self.mask_morph = cls.check_mask_morph(mask_morph)
         self.latent_size = gcfg["latent_size"]
         self.return_latents = return_latents
         self.batch_size = batch_size
@@ -127,6 +136,13 @@ class ImageGenerator:
             raise ValueError("output_downscale %d leaves %d px of the %d px output (at least 16 needed)"
                              % (f, (2 ** max_res_log2) // f, 2 ** max_res_log2))
         return f
+
+    @staticmethod
+    def check_mask_morph(v):
+        """The mask clean-up switch: a real bool (ValueError otherwise -- 1, "yes" or None are not an answer)."""
+        if not isinstance(v, bool):
+            raise ValueError("mask_morph must be True or False, got %r" % (v,))
+        return v
 
     def _get_G(self, config, device):
         return Generator(config, device=device, precision=self.precision)
@@ -325,6 +341,33 @@ class ImageGenerator:
         else:
             img, mask = self._check_out(out, n, dev)
         nptrs = [a.data_ptr() for a in noise]
+        final, mask = mask, self._raw_mask(r, mask)
+        self._run_step(model, dev, n, z, nptrs, img, mask)
+        return img, self._finish_mask(mask, final)
+
+    def _raw_mask(self, r, mask):
+        """Where the step of replica ``r`` writes its mask: ``mask`` itself, or with ``mask_morph`` a scratch tensor kept per replica,
+        batch size and stream (calls on one stream are ordered, so they may share it) -- the same address every call, so a captured
+        graph that bakes it in stays valid whatever ``mask`` is."""
+        if not self.mask_morph:
+            return mask
+        cache = self.__dict__.setdefault("_raw_masks", {})
+        key = (r, mask.shape[0], torch.cuda.current_stream(mask.device).cuda_stream)
+        raw = cache.get(key)
+        if raw is None:
+            raw = cache[key] = torch.empty_like(mask)
+        return raw
+
+    @staticmethod
+    def _finish_mask(raw, final):
+        """The mask a fused call returns: with ``mask_morph`` the clean-up of the raw one, one eager launch behind the step on the
+        same stream (never part of a captured graph)."""
+        if raw is final:
+            return final
+        return _mask_ops.morph_mask(raw, out=final)
+
+    def _run_step(self, model, dev, n, z, nptrs, img, mask):
+        """The z step into ``img`` / ``mask``: eager, or replayed from a hipGraph."""
         if self._graph_wanted(model, n):
             # A small step is a latency chain of ~100 launches of 10-60 us: when the very same call comes again (same batch,
             # same input and output addresses -- a steady loop over preallocated or recycled tensors) often enough it is replayed
@@ -338,7 +381,7 @@ class ImageGenerator:
             hit = cache.get(key)
             if hit is not None:
                 hit.replay()
-                return img, mask
+                return
             seen = model.__dict__.setdefault("_graph_seen", {})
             seen[key] = seen.get(key, 0) + 1
             # Capturing costs about as much as a few steps: a call is captured only after it has come `graph_after` (32) times
@@ -354,9 +397,8 @@ class ImageGenerator:
                 model.__dict__["_graph_captures"] = model.__dict__.get("_graph_captures", 0) + 1      # only a capture that succeeded counts
                 graph.replay()
                 cache[key] = graph
-                return img, mask
+                return
         self._step(model.ctx, current_stream_ptr(dev), n, z, nptrs, img, mask, self.output_downscale)
-        return img, mask
 
     @staticmethod
     def _step(ctx, stream, n, z, nptrs, img, mask, factor):
@@ -378,12 +420,13 @@ class ImageGenerator:
         else:
             img, mask = self._check_out(out, n, dev)
         nptrs = [a.data_ptr() for a in noise]
+        final, mask = mask, self._raw_mask(r, mask)
         if self.output_downscale == 1:
             g._model.ctx.generate_w(current_stream_ptr(dev), n, dl.data_ptr(), g.num_style_layers, nptrs, img.data_ptr(), mask.data_ptr())
         else:
             g._model.ctx.generate_downscaled(current_stream_ptr(dev), n, None, dl.data_ptr(), g.num_style_layers, nptrs,
                                              self.output_downscale, img.data_ptr(), mask.data_ptr())
-        return img, mask
+        return img, self._finish_mask(mask, final)
 
     @staticmethod
     def _capture(model, dev, n, z, nptrs, img, mask, factor=1):

@@ -5,7 +5,8 @@ is out of scope.
 
 Writes ``img_%06d.jpg`` (RGB image; the reference flips to BGR only because cv2 expects it)
 and ``mask_%06d.png`` (single channel, class index) into BASE_DIR/dataset/train_generated, at R/f px with the additive
-key ``OUTPUT_DOWNSCALE: f`` (1, 2, 4 or 8; default 1).
+key ``OUTPUT_DOWNSCALE: f`` (1, 2, 4 or 8; default 1).  The additive key ``MASK_MORPH: true`` (default false) cleans every mask on
+the GPU with the 5x5 close + open of reference utils.morph_mask before it is written (``mask_ops.morph_mask``).
 With torchrun (one process per GPU) the sample indices are sharded across ranks and every rank
 writes its own files -- no collective is needed when the sink is the filesystem.
 """
@@ -70,6 +71,7 @@ def generate(cfg, limit=None, workers=None):
     style_mix_prob = float(cfg.get("STYLE_MIX_PROB", 0.0))    # additive key: share of style-mixed samples (style_mix.py)
     # additive key: write the pairs at R/f (box-filtered image, block-summed logits' argmax); checked before any model is loaded
     downscale = ImageGenerator.check_output_downscale(cfg.get("OUTPUT_DOWNSCALE", 1), GAN_MAX_RES_LOG2[gan])
+    mask_morph = ImageGenerator.check_mask_morph(cfg.get("MASK_MORPH", False))    # additive key, checked here as well
 
     solver = SegSolver(GAN_MAX_RES_LOG2[gan], os.path.join(root_dir, "data"), os.path.join(root_dir, "checkpoints"),
                        gpu_ids=solver_ids, keep_weights=False, precision=precision)
@@ -77,7 +79,8 @@ def generate(cfg, limit=None, workers=None):
         print("train Decoder first!")   # reference main.py:82-84
         return -1
     netG = ImageGenerator(gpu_ids=gan_ids, gan_dir=gan_dir, gan=gan, batch_size=batch, precision=precision,
-                          truncation_psi=truncation_psi, style_mix_prob=style_mix_prob, output_downscale=downscale)
+                          truncation_psi=truncation_psi, style_mix_prob=style_mix_prob, output_downscale=downscale,
+                          mask_morph=mask_morph)
     netG.attach_decoder(solver.cfg, solver.net)
     dst_dir = os.path.join(root_dir, "dataset", "train_generated")
     os.makedirs(dst_dir, exist_ok=True)

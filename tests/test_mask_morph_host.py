@@ -1,0 +1,315 @@
+"""The mask clean-up without a GPU (include/gsa_mask.h; mask_ops.morph_mask; ImageGenerator(mask_morph=...); the MASK_MORPH key;
+DESIGN.md section 14).
+
+``rule_morph(m)`` is the canonical rule in numpy: D(E(E(D(m)))) with the 5x5 all-ones element, taps outside the image skipped at
+every stage.  It is PINNED here, with zero differing bytes allowed, against
+* scipy.ndimage's grey_dilation / grey_erosion chain and its grey_opening(grey_closing(...)) (mode='nearest'),
+* Pillow's MaxFilter(5) / MinFilter(5) chain (where H, W >= 5),
+* the three-stage form D5(E9(D5(m))) that the kernel uses,
+* a committed fixture (tests/golden/mask_morph.npz), which holds without scipy or Pillow.
+The GPU tests (tests/test_gpu_mask_morph.py) hold the kernel to this rule bit for bit.  Also here: hand cases, a guard that the
+inputs can tell the rule from a zero-padded erosion, the C ABI's symbols and the validation of the keyword and the key."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from tests.test_downscale_host import _ModelLoaded, _config, no_models  # noqa: F401  (no_models is a fixture)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# -- the rule ------------------------------------------------------------------------------------------------------------------
+def _window(m, radius, identity, reduce, outside=None):
+    """max / min over the (2*radius+1)^2 window on the last two axes; the outside of the image holds ``identity`` (the rule: the
+    tap is skipped) or, for the wrong variants of the guard, ``outside``."""
+    m = np.asarray(m)
+    assert m.dtype == np.uint8 and m.ndim >= 2
+    H, W = m.shape[-2:]
+    pad = [(0, 0)] * (m.ndim - 2) + [(radius, radius)] * 2
+    p = np.pad(m, pad, constant_values=identity if outside is None else outside)
+    out = np.full(m.shape, identity, np.uint8)
+    for dy in range(2 * radius + 1):
+        for dx in range(2 * radius + 1):
+            out = reduce(out, p[..., dy:dy + H, dx:dx + W])
+    return out
+
+
+def dilate(m, radius=2):
+    return _window(m, radius, 0, np.maximum)
+
+
+def erode(m, radius=2):
+    return _window(m, radius, 255, np.minimum)
+
+
+def rule_morph(m):
+    """(H, W) or (n, H, W) u8 -> the same shape: close then open, every image of a batch on its own."""
+    return dilate(erode(erode(dilate(m))))
+
+
+def rule_three_stage(m):
+    """The form the kernel may use: two skipped-border 5x5 erosions are one skipped-border 9x9 erosion."""
+    return dilate(erode(dilate(m), radius=4))
+
+
+def zero_border_morph(m):
+    """The BUG the tests must catch: erosions that see a zero-padded outside eat the border."""
+    def bad_erode(a):
+        return _window(a, 2, 255, np.minimum, outside=0)
+    return dilate(bad_erode(bad_erode(dilate(m))))
+
+
+# -- the inputs ----------------------------------------------------------------------------------------------------------------
+def _blur(a, sigma=2.0):
+    """Separable Gaussian with edge replication (numpy only)."""
+    r = int(3 * sigma)
+    k = np.exp(-0.5 * (np.arange(-r, r + 1) / sigma) ** 2)
+    k /= k.sum()
+    for axis in (-2, -1):
+        pad = [(0, 0)] * a.ndim
+        pad[axis] = (r, r)
+        p = np.pad(a, pad, mode="edge")
+        a = sum(k[i] * np.take(p, range(i, i + a.shape[axis]), axis=axis) for i in range(2 * r + 1))
+    return a
+
+
+def blobs(seed, shape):
+    """Thresholded smooth noise with 3 % salt-and-pepper: what a decoder's mask looks like, flipped pixels and pinholes included."""
+    rng = np.random.default_rng([seed, 1])
+    m = (_blur(rng.standard_normal(shape)) > 0).astype(np.uint8)
+    flip = rng.random(shape) < 0.03
+    return np.where(flip, 1 - m, m).astype(np.uint8)
+
+
+def frame(shape, value=1, inside=0):
+    """A 1-px frame of ``value`` on the image border around ``inside``."""
+    m = np.full(shape, inside, np.uint8)
+    m[..., 0, :] = m[..., -1, :] = m[..., :, 0] = m[..., :, -1] = value
+    return m
+
+
+RANDOM_KINDS = ("sparse", "half", "dense", "blobs", "classes", "bytes")
+CONSTANT_KINDS = ("zeros", "ones", "all255", "frame", "frame0")
+KINDS = RANDOM_KINDS + CONSTANT_KINDS
+
+
+def make(kind, seed, shape):
+    """One seeded input of every kind the issue lists."""
+    rng = np.random.default_rng([seed, KINDS.index(kind)])
+    if kind in ("sparse", "half", "dense"):
+        return (rng.random(shape) < {"sparse": 0.02, "half": 0.5, "dense": 0.98}[kind]).astype(np.uint8)
+    if kind == "blobs":
+        return blobs(seed, shape)
+    if kind == "classes":
+        return rng.integers(0, 8, shape, dtype=np.uint8)
+    if kind == "bytes":
+        m = rng.integers(0, 256, shape, dtype=np.uint8)
+        m.reshape(-1)[:2] = (0, 255)[:m.size]       # the padding identities are among the values
+        return m
+    if kind == "frame":
+        return frame(shape)
+    if kind == "frame0":        # the frame in the other polarity: a border of zeros around ones
+        return frame(shape, 0, 1)
+    return np.full(shape, {"zeros": 0, "ones": 1, "all255": 255}[kind], np.uint8)
+
+
+SMALL_SHAPES = [(1, 1, 1), (1, 1, 7), (1, 9, 2), (1, 3, 5), (1, 5, 5), (2, 16, 16), (1, 17, 23)]     # both sides clip at once
+SEAM_SHAPES = [(1, 200, 328), (1, 40, 56), (1, 130, 70)]
+SHAPES = SMALL_SHAPES + SEAM_SHAPES
+
+
+def cases():
+    for shape in SHAPES:
+        for kind in KINDS:
+            yield shape, kind, make(kind, sum(shape), shape)
+
+
+def _differing(got, want):
+    assert got.shape == want.shape and got.dtype == want.dtype == np.uint8
+    return int((got != want).sum())
+
+
+# -- the pins ------------------------------------------------------------------------------------------------------------------
+def test_rule_equals_scipys_grey_morphology():
+    ndi = pytest.importorskip("scipy.ndimage")
+    for shape, kind, m in cases():
+        for plane, want in zip(m, rule_morph(m)):
+            kw = dict(size=(5, 5), mode="nearest")
+            chain = ndi.grey_dilation(ndi.grey_erosion(ndi.grey_erosion(ndi.grey_dilation(plane, **kw), **kw), **kw), **kw)
+            assert _differing(chain, want) == 0, (shape, kind)
+            assert _differing(ndi.grey_opening(ndi.grey_closing(plane, **kw), **kw), want) == 0, (shape, kind)
+            assert _differing(ndi.grey_dilation(plane, **kw), dilate(plane)) == 0, (shape, kind)
+            assert _differing(ndi.grey_erosion(plane, **kw), erode(plane)) == 0, (shape, kind)
+
+
+def test_rule_equals_pillows_rank_filters():
+    pytest.importorskip("PIL")
+    from PIL import Image, ImageFilter
+    mx, mn = ImageFilter.MaxFilter(5), ImageFilter.MinFilter(5)
+    seen = 0
+    for shape, kind, m in cases():
+        if shape[1] < 5 or shape[2] < 5:
+            continue
+        for plane, want in zip(m, rule_morph(m)):
+            got = np.asarray(Image.fromarray(plane, "L").filter(mx).filter(mn).filter(mn).filter(mx))
+            assert _differing(got, want) == 0, (shape, kind)
+            seen += 1
+    assert seen >= 5 * len(KINDS)
+
+
+def test_rule_equals_the_three_stage_form():
+    for shape, kind, m in cases():
+        assert _differing(rule_three_stage(m), rule_morph(m)) == 0, (shape, kind)
+
+
+def test_rule_reproduces_the_committed_results():
+    """The same pin without scipy: what scipy.ndimage computed (tests/golden/make_mask_morph_golden.py)."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "mask_morph.npz"))
+    keys = sorted(k[:-5] for k in g.files if k.endswith("_mask"))
+    assert len(keys) >= 4
+    changed = 0
+    for k in keys:
+        m, want = g[k + "_mask"], g[k + "_morph"]
+        assert m.shape[-2] <= 64 and m.shape[-1] <= 64
+        assert _differing(rule_morph(m), want) == 0, k
+        changed += int((m != want).sum())
+    assert changed > 0, "the rule changed nothing: the fixture pins nothing"
+
+
+def test_every_random_input_is_changed_by_the_rule():
+    """A copy kernel cannot pass the GPU tests: on every random kind at every shape of 16 px and more the rule moves a pixel; on
+    blobs it moves roughly a seventh of them."""
+    for shape, kind, m in cases():
+        if kind in RANDOM_KINDS and min(shape[1:]) >= 16:
+            assert _differing(rule_morph(m), m) > 0, (shape, kind)
+    m = make("blobs", 3, (1, 200, 328))
+    share = _differing(rule_morph(m), m) / m.size
+    assert 0.05 < share < 0.30, share
+
+
+# -- hand cases ----------------------------------------------------------------------------------------------------------------
+def test_hand_cases():
+    z = np.zeros((24, 24), np.uint8)
+    one = np.ones((24, 24), np.uint8)
+    m = z.copy()
+    m[11, 12] = 1
+    assert not rule_morph(m).any(), "a single pixel vanishes"
+    m = one.copy()
+    m[11, 12] = 0
+    assert rule_morph(m).all(), "a single hole fills"
+    m = z.copy()
+    m[6:10, 7:11] = 1
+    assert not rule_morph(m).any(), "a 4x4 blob vanishes"
+    m = z.copy()
+    m[6:11, 7:12] = 1
+    assert np.array_equal(rule_morph(m), m), "a 5x5 blob survives"
+    m = one.copy()
+    m[6:10, 7:11] = 0
+    assert rule_morph(m).all(), "a 4x4 hole in ones fills"
+    for v in (0, 1, 255):
+        for shape in ((24, 24), (1, 1), (3, 7), (2, 9, 4)):
+            c = np.full(shape, v, np.uint8)
+            assert np.array_equal(rule_morph(c), c), "constant %d at %s is a fixed point" % (v, shape)
+
+
+def test_every_image_of_a_batch_is_a_plane_of_its_own():
+    batch = np.stack([np.ones((32, 32), np.uint8), np.zeros((32, 32), np.uint8), blobs(5, (32, 32))])
+    out = rule_morph(batch)
+    for i in range(3):
+        assert np.array_equal(out[i], rule_morph(batch[i]))
+    assert out[0].all() and not out[1].any()
+    assert rule_morph(batch[:0]).shape == (0, 32, 32)
+
+
+def test_the_inputs_can_tell_the_rule_from_a_zero_padded_erosion():
+    """Guard: the all-ones and the border-frame cases are in the set BECAUSE a form whose erosions see zeros outside the image fails
+    them.  The frame that does it is the frame of zeros around ones (the close fills it from the inside: the rule returns all ones);
+    a 1-px frame of ONES is thinner than the element, so the open removes it under either border and that polarity separates
+    nothing -- asserted too, so nobody takes it for a guard."""
+    for shape in SHAPES:
+        ones, ring, ring1 = make("ones", 0, shape), make("frame0", 0, shape), make("frame", 0, shape)
+        assert np.array_equal(rule_morph(ones), ones)
+        assert _differing(zero_border_morph(ones), ones) > 0, shape
+        if min(shape[1:]) >= 3:                 # smaller, the frame is the whole image: all zeros
+            assert _differing(zero_border_morph(ring), rule_morph(ring)) > 0, shape
+        if min(shape[1:]) >= 7:
+            assert rule_morph(ring).all(), shape
+        if min(shape[1:]) >= 12:
+            assert not rule_morph(ring1).any() and not zero_border_morph(ring1).any(), shape
+
+
+# -- the C ABI -----------------------------------------------------------------------------------------------------------------
+def test_mask_header_symbols_are_exported(hip_library):
+    """include/gsa_mask.h <-> library exports <-> the ctypes table of mask_ops."""
+    with open(os.path.join(ROOT, "include", "gsa_mask.h")) as f:
+        header = f.read()
+    declared = set(re.findall(r"\bint\s+(gsa_mask_[a-z0-9_]+)\s*\(", header))
+    assert declared == {"gsa_mask_morph"}
+    lib = ctypes.CDLL(hip_library)
+    for name in declared:
+        assert hasattr(lib, name), "%s declared in gsa_mask.h but not exported" % name
+    from gan_segmentation_amd import mask_ops
+    assert set(mask_ops._api().keys()) == declared
+
+
+def test_morph_rejects_bad_arguments_before_touching_the_gpu(hip_library):
+    """Argument validation of gsa_mask_morph happens on the host (no HIP call precedes it): a negative batch, sizes outside 1..65535,
+    null or overlapping pointers; an empty batch is a successful no-op."""
+    from gan_segmentation_amd import mask_ops
+    fn = mask_ops._api()["gsa_mask_morph"]
+    good = dict(n=2, H=32, W=48, mask=1 << 20, out=2 << 20)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return fn(None, a["n"], a["H"], a["W"], a["mask"], a["out"])
+
+    for bad in (dict(n=-1), dict(H=0), dict(W=0), dict(H=65536), dict(W=65536), dict(H=-4), dict(mask=None), dict(out=None),
+                dict(out=1 << 20), dict(out=(1 << 20) + 2 * 32 * 48 - 1), dict(mask=(2 << 20) + 1), dict(n=1 << 14, H=65535, W=65535)):
+        assert call(**bad) == -1, bad
+    assert call(n=0) == 0 and call(n=0, mask=None, out=None) == 0
+
+
+def test_morph_mask_checks_its_tensors_before_any_gpu_work():
+    import torch
+    from gan_segmentation_amd import mask_ops
+    for bad in (torch.zeros((4, 4), dtype=torch.uint8), torch.zeros((1, 4, 4), dtype=torch.float32), np.zeros((4, 4), np.uint8), None):
+        with pytest.raises(ValueError, match="mask"):
+            mask_ops.morph_mask(bad)
+
+
+# -- the keyword and the key ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("value", [1, 0, "yes", "true", None, 1.0, np.bool_(True)])
+def test_mask_morph_rejects_what_is_not_a_bool(value):
+    from gan_segmentation_amd import weights as W
+    from gan_segmentation_amd.image_generator import ImageGenerator
+    with pytest.raises(ValueError, match="mask_morph"):
+        ImageGenerator.check_mask_morph(value)
+    with pytest.raises(ValueError, match="mask_morph"):
+        ImageGenerator.from_params(W.reduced_generator_config(7), {}, gpu_ids=[0], mask_morph=value)
+
+
+def test_mask_morph_accepts_both_booleans_and_defaults_to_off():
+    import inspect
+    from gan_segmentation_amd.image_generator import ImageGenerator
+    assert ImageGenerator.check_mask_morph(True) is True and ImageGenerator.check_mask_morph(False) is False
+    assert ImageGenerator.mask_morph is False
+    for fn in (ImageGenerator.__init__, ImageGenerator.from_params):
+        assert inspect.signature(fn).parameters["mask_morph"].default is False
+
+
+@pytest.mark.parametrize("value", [2, 1, "yes", 0.5])
+def test_cli_rejects_a_bad_key_before_loading_a_model(tmp_path, no_models, value):
+    from gan_segmentation_amd import main as cli
+    with pytest.raises(ValueError, match="mask_morph"):
+        cli.main(["generate", "--config", _config(tmp_path, MASK_MORPH=value)])
+
+
+def test_cli_accepts_the_key_and_its_default(tmp_path, no_models):
+    from gan_segmentation_amd import main as cli
+    for keys in ({}, {"MASK_MORPH": True}, {"MASK_MORPH": False}):
+        with pytest.raises(_ModelLoaded):
+            cli.main(["generate", "--config", _config(tmp_path, **keys)])
+    assert "MASK_MORPH" in cli.__doc__
