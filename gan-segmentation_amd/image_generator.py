@@ -36,6 +36,7 @@ import torch
 from . import augment as _augment
 from . import jpeg as _jpeg
 from . import mask_ops as _mask_ops
+from . import photometric as _photometric
 from . import style_mix as _style_mix
 from . import weights as _weights
 from ._runtime import current_stream_ptr, split_sizes, to_device_f32
@@ -242,7 +243,7 @@ class ImageGenerator:
 
     def training_batches(self, batch, crop=480, mode="train", seed=0, first_index=0, num_samples=None, rank=0, world=1,
                          mean=_augment.IMAGENET_MEAN, std=_augment.IMAGENET_STD, dtype=torch.float32, labels="uint8",
-                         ignore_label=_augment.IGNORE_LABEL, jpeg_quality=None, **limits):
+                         ignore_label=_augment.IGNORE_LABEL, jpeg_quality=None, photometric=None, **limits):
         """The training stream: an iterator of ``(image (n, C, crop, crop) dtype, label (n, crop, crop), first_index)``.
 
         Batch k of the global sequence holds the samples ``first_index + k*batch ..`` and goes to the rank with ``k % world == rank``
@@ -255,8 +256,11 @@ class ImageGenerator:
         the caller's current stream: the consumer may keep them.  ``jpeg_quality=q`` (an int in 1..100; 95 is what ``main.py generate``
         stores) passes every image through ``jpeg.roundtrip`` in front of the warp: the stream then carries exactly the pixels a
         reader of the dataset's quality-q JPEG files would decode (three channels and a pair size that is a multiple of 16 wanted;
-        the mask is untouched, PNG is lossless).  ``None``, the default, leaves the image as generated.  Arguments are checked here,
-        before any GPU work."""
+        the mask is untouched, PNG is lossless).  ``None``, the default, leaves the image as generated.  ``photometric`` changes the
+        pixels' values between the round trip and the warp (``photometric.photometric``: contrast, brightness, channel shift, a
+        Gaussian blur, noise; the warp's border stays black and the mask is untouched): ``True`` takes the default limits, a dict
+        gives limits (``photometric.DEFAULT_LIMITS`` names them), ``None``, the default, leaves the values alone.  Its plan is a
+        function of ``(seed, index)`` like the warp's.  Arguments are checked here, before any GPU work."""
         if self._decoder is None:
             raise RuntimeError("attach_decoder() first")
         crop, mode = _augment.check_crop(crop), _augment.check_mode(mode)
@@ -275,18 +279,25 @@ class ImageGenerator:
         if jpeg_quality is not None:
             jpeg_quality = _jpeg.check_quality(jpeg_quality, "jpeg_quality")
             _jpeg.check_roundtrip_shape(R, R, nc)
+        photometric = _photometric.check_keyword(photometric)
+        if photometric is not None:
+            _photometric.check_shape(R, R, nc)
         batches = _augment.stream_batches(first_index, batch, num_samples, rank, world)
         return self._training_batches(batches, seed, R, crop, mode, limits, out_size, scale, bias, dtype, labels, int(ignore_label),
-                                      jpeg_quality)
+                                      jpeg_quality, photometric)
 
     def _training_batches(self, batches, seed, R, crop, mode, limits, out_size, scale, bias, dtype, labels, ignore_label,
-                          jpeg_quality=None):
+                          jpeg_quality=None, photometric=None):
         dev0 = self._gens[0]._model.device
         for first, n in batches:
             img, mask = self.generate_indexed(first, n, seed=seed)
             if jpeg_quality is not None:
                 with torch.cuda.device(dev0):
                     img = _jpeg.roundtrip(img, jpeg_quality)
+            if photometric is not None:
+                rows = _photometric.photometric_plan(seed, first, n, **photometric)
+                with torch.cuda.device(dev0):
+                    img = _photometric.photometric(img, rows, seed, first)
             matrices = _augment.plan_matrices(seed, first, n, R, R, crop, mode, **limits)
             with torch.cuda.device(dev0):
                 image, label = _augment.augment_pairs(img, mask, matrices, out_size, scale=scale, bias=bias, dtype=dtype,
