@@ -109,9 +109,13 @@ STATUS_RING_DEPTH = 32      # pinned status slots ImageGenerator.snapshot_status
 
 
 class DatasetWriter:
-    """``submit(img, mask, first_index)`` returns immediately; ``close()`` waits for every file."""
+    """``submit(img, mask, first_index)`` returns immediately; ``close()`` waits for every file.
 
-    def __init__(self, dst_dir, workers=None, slots=3, jpeg_quality=95, gpu_jpeg=False, jpeg_restart=None, gpu_png=False):
+    ``stats=True``: every submitted batch also goes through ``pair_stats.pair_stats`` on the producing stream; the 88-word rows
+    travel to the host with the batch and ``close()`` writes those of the batches whose files were released into one
+    ``pair_stats_<first>_<last + 1>.npz`` beside the pairs (``pair_stats.merge_shards`` reads them back)."""
+
+    def __init__(self, dst_dir, workers=None, slots=3, jpeg_quality=95, gpu_jpeg=False, jpeg_restart=None, gpu_png=False, stats=False):
         if not 1 <= slots < STATUS_RING_DEPTH:
             raise ValueError("slots must be in [1, %d): a batch's status slot (ImageGenerator.snapshot_status) is reused after "
                              "%d later batches" % (STATUS_RING_DEPTH, STATUS_RING_DEPTH))
@@ -139,6 +143,11 @@ class DatasetWriter:
         self._dispatcher.start()
         self.written = 0
         self.submitted = 0
+        self.stats = bool(stats)
+        self.stats_path = None               # the shard file close() wrote
+        self._stat_size = None               # (H, W, C) of the pairs
+        self._stat_pending = {}              # first_index -> pinned rows of that batch, valid once its event has completed
+        self._stat_rows = []                 # (first_index, rows) of the batches whose files were released
 
     # -- producer side ----------------------------------------------------------------------
     def submit(self, img, mask, first_index, status=None):
@@ -148,6 +157,9 @@ class DatasetWriter:
         the batch's files -- and every later one -- if a device-side check had failed by then (``DeviceCheckFailed``)."""
         if self._errors:
             raise self._errors[0]
+        if self.stats and isinstance(img, np.ndarray):
+            raise ValueError("DatasetWriter(stats=True) takes CUDA tensors: the statistics pass has no CPU path")
+        rows = self._launch_stats(img, mask) if self.stats else None      # on the producing stream, before anything is queued
         self.submitted += int(img.shape[0])
         with self._lock:
             self._status[first_index] = status
@@ -158,7 +170,7 @@ class DatasetWriter:
         slot = self._free.get()               # back-pressure: at most `slots` batches in flight
         n = img.shape[0]
         if self.gpu_jpeg or self.gpu_png:
-            return self._submit_encoded(slot, img, mask, first_index)
+            return self._submit_encoded(slot, img, mask, first_index, rows)
         buf = self._host[slot]
         if buf is None or buf[0].shape[0] < n or buf[0].shape[1:] != img.shape[1:]:
             buf = (torch.empty(tuple(img.shape), dtype=torch.uint8).pin_memory(),
@@ -171,11 +183,38 @@ class DatasetWriter:
         with torch.cuda.stream(self._copy_stream):
             buf[0][:n].copy_(img, non_blocking=True)
             buf[1][:n].copy_(mask, non_blocking=True)
+            self._stage_stats(slot, rows, first_index)
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
         img.record_stream(self._copy_stream)
         mask.record_stream(self._copy_stream)
         self._pending.put((slot, ev, buf[0][:n].numpy(), buf[1][:n].numpy(), first_index))
+
+    def _launch_stats(self, img, mask):
+        """The statistics pass on the producing stream, right behind the kernels that wrote the pair -> device rows (n, 88)."""
+        from . import pair_stats
+        size = (int(img.shape[1]), int(img.shape[2]), int(img.shape[3]))
+        if self._stat_size is None:
+            self._stat_size = size
+        elif size != self._stat_size:
+            raise ValueError("DatasetWriter(stats=True): one shard file holds pairs of one size, got %s after %s" % (size, self._stat_size))
+        return pair_stats.pair_stats(img if img.is_contiguous() else img.contiguous(),
+                                     mask if mask.is_contiguous() else mask.contiguous())
+
+    def _stage_stats(self, slot, rows, first_index):
+        """On the copy stream, with the batch: the rows into the slot's pinned staging."""
+        if rows is None:
+            return
+        import torch
+        n = rows.shape[0]
+        stage = self._stage[slot].get("stats")
+        if stage is None or stage.shape[0] < n:
+            stage = torch.empty(tuple(rows.shape), dtype=torch.int64).pin_memory()
+            self._stage[slot]["stats"] = stage
+        stage[:n].copy_(rows, non_blocking=True)
+        rows.record_stream(self._copy_stream)
+        with self._lock:
+            self._stat_pending[first_index] = stage[:n].numpy()
 
     def _encoder(self, slot, kind, n, H, W, device):
         enc = self._encoders[slot].get(kind)
@@ -191,7 +230,7 @@ class DatasetWriter:
             self._encoders[slot][kind] = enc
         return enc
 
-    def _submit_encoded(self, slot, img, mask, first_index):
+    def _submit_encoded(self, slot, img, mask, first_index, rows=None):
         """Compress on the GPU right behind the generate kernels; the dispatcher thread then fetches the lengths and
         exactly the compressed bytes.  Whatever is not compressed on the GPU is copied out raw, as in the host path."""
         import torch
@@ -229,6 +268,7 @@ class DatasetWriter:
                 raw = pinned("raw_mask", mask)
                 raw.copy_(mask, non_blocking=True)
                 payload["mask"] = raw.numpy()
+            self._stage_stats(slot, rows, first_index)
             ev = torch.cuda.Event()
             ev.record(self._copy_stream)
         img.record_stream(self._copy_stream)
@@ -264,6 +304,8 @@ class DatasetWriter:
                 return
             slot, ev, img, mask, first = item
             futs = []
+            with self._lock:
+                stat_rows = self._stat_pending.pop(first, None)
             try:
                 if ev is not None:
                     ev.synchronize()
@@ -294,6 +336,8 @@ class DatasetWriter:
                 else:
                     futs = [self.pool.submit(write_pair, self.dst_dir, first + i, img[i], mask[i], self.jpeg_quality)
                             for i in range(img.shape[0])]
+                if stat_rows is not None:     # the files of this batch are released: its rows count (copied out of the slot's staging)
+                    self._stat_rows.append((first, np.array(stat_rows)))
             except Exception as e:   # surfaced by the next submit()/close()
                 self._errors.append(e)
             # The dispatcher does not wait for the files: the batch's slot (its pinned buffers) is released by the
@@ -344,6 +388,11 @@ class DatasetWriter:
         self._pending.put(None)
         self._dispatcher.join()
         self.pool.shutdown(wait=True)
+        if self._stat_rows and self.stats_path is None:
+            from . import pair_stats
+            index = np.concatenate([np.arange(first, first + len(rows), dtype=np.int64) for first, rows in self._stat_rows])
+            self.stats_path = pair_stats.save_shard(self.dst_dir, index, np.concatenate([rows for _f, rows in self._stat_rows]),
+                                                    *self._stat_size)
         if self._errors:
             raise self._errors[0]
         return self.written

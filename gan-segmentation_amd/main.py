@@ -6,7 +6,9 @@ is out of scope.
 Writes ``img_%06d.jpg`` (RGB image; the reference flips to BGR only because cv2 expects it)
 and ``mask_%06d.png`` (single channel, class index) into BASE_DIR/dataset/train_generated, at R/f px with the additive
 key ``OUTPUT_DOWNSCALE: f`` (1, 2, 4 or 8; default 1).  The additive key ``MASK_MORPH: true`` (default false) cleans every mask on
-the GPU with the 5x5 close + open of reference utils.morph_mask before it is written (``mask_ops.morph_mask``).
+the GPU with the 5x5 close + open of reference utils.morph_mask before it is written (``mask_ops.morph_mask``).  The additive key
+``PAIR_STATS: true`` (default false) adds one ``pair_stats_<first>_<last + 1>.npz`` per rank with the per-sample statistics of the
+written pairs (``pair_stats.pair_stats``); ``python -m gan_segmentation_amd.pair_stats DIR`` merges them into a report.
 With torchrun (one process per GPU) the sample indices are sharded across ranks and every rank
 writes its own files -- no collective is needed when the sink is the filesystem.
 """
@@ -55,6 +57,7 @@ def generate(cfg, limit=None, workers=None):
     from . import dist as gdist
     from .dataset_writer import DatasetWriter, DeviceCheckFailed
     from .image_generator import ImageGenerator
+    from .pair_stats import check_pair_stats
     from .seg_solver import SegSolver
     from .weights import GAN_MAX_RES_LOG2
 
@@ -72,6 +75,7 @@ def generate(cfg, limit=None, workers=None):
     # additive key: write the pairs at R/f (box-filtered image, block-summed logits' argmax); checked before any model is loaded
     downscale = ImageGenerator.check_output_downscale(cfg.get("OUTPUT_DOWNSCALE", 1), GAN_MAX_RES_LOG2[gan])
     mask_morph = ImageGenerator.check_mask_morph(cfg.get("MASK_MORPH", False))    # additive key, checked here as well
+    stats = check_pair_stats(cfg.get("PAIR_STATS", False))    # additive key, checked here as well: every rank writes its own shard file
 
     solver = SegSolver(GAN_MAX_RES_LOG2[gan], os.path.join(root_dir, "data"), os.path.join(root_dir, "checkpoints"),
                        gpu_ids=solver_ids, keep_weights=False, precision=precision)
@@ -91,7 +95,8 @@ def generate(cfg, limit=None, workers=None):
     # include/gsa_jpeg.h and include/gsa_png.h; the host threads only frame and write them
     on_gpu = bool(cfg.get("JPEG_ON_GPU", True))
     try:
-        with DatasetWriter(dst_dir, workers=workers, gpu_jpeg=on_gpu, gpu_png=bool(cfg.get("PNG_ON_GPU", on_gpu))) as writer:
+        with DatasetWriter(dst_dir, workers=workers, gpu_jpeg=on_gpu, gpu_png=bool(cfg.get("PNG_ON_GPU", on_gpu)),
+                           stats=stats) as writer:
             for index, bs in shard_batches(n_generate, batch, world, rank):
                 # latents and noise keyed on the global sample index: the files are the same for any number of ranks
                 img, mask = netG.generate_indexed(index, bs, seed=seed)
