@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI declared in include/gsa.h.
+"""ctypes binding of the C ABI declared in the headers under include/: one signature table, bound in one place.
 
 ``load_library()`` opens the HIP library built in-tree by ``__graft_entry__.build()``
 (csrc/libgsa_hip.so).  There is no CPU fallback: if the library is missing or a call
@@ -16,17 +16,6 @@ EXPERIMENTS_LIBRARY = os.path.join(_HERE, "csrc", "libgsa_hip_exp.so")      # `m
 if os.environ.get("GSA_HIP_LIBRARY"):      # tests / A-B runs: another build of the same library (a file name inside csrc/, or a path)
     _alt = os.environ["GSA_HIP_LIBRARY"]
     HIP_LIBRARY = _alt if os.path.isabs(_alt) else os.path.join(_HERE, "csrc", _alt)
-
-# every symbol include/gsa.h declares
-API_SYMBOLS = (
-    "create", "destroy", "last_error", "generator_init", "generator_set_param",
-    "generator_commit", "decoder_init", "decoder_set_param", "decoder_commit", "reserve",
-    "generator_forward", "decoder_forward", "generate", "set_overlap", "set_precision", "segmentation_eval", "fill_inputs",
-    "profile_enable", "profile_collect",
-    "profile_entry", "profile_reset", "version", "check", "status_snapshot", "debug_inject",
-    "mapping_forward", "generator_forward_w", "generate_w", "generate_downscaled",
-)
-
 
 class GsaError(RuntimeError):
     pass
@@ -48,65 +37,121 @@ class DecoderConfig(ctypes.Structure):
                 ("in_channels", ctypes.POINTER(ctypes.c_int32))]
 
 
-class Api:
-    """Function table of one shared library exporting ``<prefix>create`` ... ."""
+_c = ctypes
+_vp, _i32, _i64, _u64, _f32, _int = _c.c_void_p, _c.c_int32, _c.c_int64, _c.c_uint64, _c.c_float, _c.c_int
+_vpp = _c.POINTER(_vp)
+_bn = [_vp, _i32, _i32, _i32]       # stream, n, C, HW: the head of every batch-norm entry
 
-    def __init__(self, path, prefix="gsa_", optional=()):
+# Every function the headers under include/ declare: header -> {name: (result type, argument types)}.  The ONE place a C signature
+# is restated in Python; tests/test_abi_and_host.py checks it against the headers' text, kind by kind.
+SIGNATURES = {
+    "gsa.h": {
+        "gsa_create": (_int, [_int, _vpp]),
+        "gsa_destroy": (None, [_vp]),
+        "gsa_last_error": (_c.c_char_p, [_vp]),
+        "gsa_generator_init": (_int, [_vp, _c.POINTER(GeneratorConfig)]),
+        "gsa_generator_set_param": (_int, [_vp, _c.c_char_p, _vp, _i32, _c.POINTER(_i64)]),
+        "gsa_generator_commit": (_int, [_vp]),
+        "gsa_decoder_init": (_int, [_vp, _c.POINTER(DecoderConfig)]),
+        "gsa_decoder_set_param": (_int, [_vp, _c.c_char_p, _vp, _i32, _c.POINTER(_i64)]),
+        "gsa_decoder_commit": (_int, [_vp]),
+        "gsa_reserve": (_int, [_vp, _i32]),
+        "gsa_generator_forward": (_int, [_vp, _vp, _i32, _vp, _vpp, _i32, _vp, _vp, _vpp, _i32]),
+        "gsa_decoder_forward": (_int, [_vp, _vp, _i32, _vpp, _i32, _vp, _vp]),
+        "gsa_generate": (_int, [_vp, _vp, _i32, _vp, _vpp, _i32, _vp, _vp]),
+        "gsa_mapping_forward": (_int, [_vp, _vp, _i32, _vp, _vp]),
+        "gsa_generator_forward_w": (_int, [_vp, _vp, _i32, _vp, _i32, _vpp, _i32, _vp, _vp, _vpp, _i32]),
+        "gsa_generate_w": (_int, [_vp, _vp, _i32, _vp, _i32, _vpp, _i32, _vp, _vp]),
+        "gsa_generate_downscaled": (_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vpp, _i32, _i32, _vp, _vp]),
+        "gsa_set_overlap": (_int, [_vp, _i32]),
+        "gsa_set_precision": (_int, [_vp, _i32]),
+        "gsa_segmentation_eval": (_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+        "gsa_fill_inputs": (_int, [_vp, _vp, _i32, _u64, _u64, _vp, _vpp, _i32]),
+        "gsa_profile_enable": (_int, [_vp, _i32]),
+        "gsa_profile_collect": (_int, [_vp]),
+        "gsa_profile_entry": (_int, [_vp, _i32, _c.POINTER(_c.c_char_p), _c.POINTER(_c.c_double), _c.POINTER(_i64),
+                                     _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+        "gsa_profile_reset": (_int, [_vp]),
+        "gsa_version": (_c.c_char_p, []),
+        "gsa_check": (_int, [_vp]),
+        "gsa_status_snapshot": (_int, [_vp, _vp, _vp]),
+        "gsa_debug_inject": (_int, [_vp, _i32, _i32]),
+    },
+    "gsa_train.h": {
+        "gsa_train_conv": (_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32]),
+        "gsa_train_conv_wgrad": (_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+        "gsa_train_bn_lrelu_fwd": (_int, _bn + [_vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _f32, _vp]),
+        "gsa_train_bn_lrelu_bwd": (_int, _bn + [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _vp]),
+        "gsa_train_bn_sums": (_int, _bn + [_vp, _vp]),
+        "gsa_train_bn_lrelu_fwd_sums": (_int, _bn + [_c.c_double, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp]),
+        "gsa_train_bn_bwd_sums": (_int, _bn + [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp]),
+        "gsa_train_bn_lrelu_bwd_sums": (_int, _bn + [_c.c_double, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+        "gsa_train_softmax_ce": (_int, _bn + [_vp, _vp, _vp, _vp, _f32]),
+        "gsa_train_upsample2_bwd": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32]),
+        "gsa_train_add": (_int, [_vp, _i64, _vp, _vp, _vp]),
+        "gsa_train_dropout_mask": (_int, [_vp, _i64, _u64, _c.c_uint32, _f32, _vp]),
+        "gsa_train_adam": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _f32, _f32]),
+    },
+    "gsa_jpeg.h": {
+        "gsa_jpeg_header": (_i64, [_i32, _i32, _i32, _i32, _vp, _i64]),
+        "gsa_jpeg_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+        "gsa_jpeg_max_scan_bytes": (_i64, [_i32, _i32, _i32]),
+        "gsa_jpeg_encode": (_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
+    },
+    "gsa_jpeg_roundtrip.h": {
+        "gsa_jpeg_roundtrip_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+        "gsa_jpeg_roundtrip": (_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp]),
+    },
+    "gsa_png.h": {
+        "gsa_png_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+        "gsa_png_max_stream_bytes": (_i64, [_i32, _i32]),
+        "gsa_png_encode": (_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
+    },
+    "gsa_augment.h": {
+        "gsa_augment_pairs": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    },
+    "gsa_mask.h": {
+        "gsa_mask_morph": (_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    },
+    "gsa_photometric.h": {
+        "gsa_photometric": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _u64, _u64, _vp]),
+    },
+    "gsa_stats.h": {
+        "gsa_pair_stats": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    },
+}
+
+
+class Api:
+    """Function table of one shared library: every entry of ``SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full
+    name; the entries of include/gsa.h are attributes without the prefix as well (``api.create``, ``api.generate``, ...)."""
+
+    def __init__(self, path, prefix="gsa_"):
         if not os.path.exists(path):
             raise GsaError("native library %s not found -- run `python -c 'import __graft_entry__ as g; "
                            "g.build()'` (there is no CPU fallback)" % path)
         self.path = path
         self.prefix = prefix
-        if prefix == "gsa_":
-            # The process must end up with ONE HIP runtime: torch brings its own libamdhip64, and a library that pulled
-            # in another copy first leaves the GPU invisible to one of the two -- so torch is imported before the dlopen.
-            import torch  # noqa: F401
+        # The process must end up with ONE HIP runtime: torch brings its own libamdhip64, and a library that pulled
+        # in another copy first leaves the GPU invisible to one of the two -- so torch is imported before the dlopen.
+        import torch  # noqa: F401
         self.lib = ctypes.CDLL(path)
-        c = ctypes
-        vp, i32 = c.c_void_p, c.c_int32
-        sig = {
-            "create": (c.c_int, [c.c_int, c.POINTER(vp)]),
-            "destroy": (None, [vp]),
-            "last_error": (c.c_char_p, [vp]),
-            "generator_init": (c.c_int, [vp, c.POINTER(GeneratorConfig)]),
-            "generator_set_param": (c.c_int, [vp, c.c_char_p, vp, i32, c.POINTER(c.c_int64)]),
-            "generator_commit": (c.c_int, [vp]),
-            "decoder_init": (c.c_int, [vp, c.POINTER(DecoderConfig)]),
-            "decoder_set_param": (c.c_int, [vp, c.c_char_p, vp, i32, c.POINTER(c.c_int64)]),
-            "decoder_commit": (c.c_int, [vp]),
-            "reserve": (c.c_int, [vp, i32]),
-            "generator_forward": (c.c_int, [vp, vp, i32, vp, c.POINTER(vp), i32, vp, vp, c.POINTER(vp), i32]),
-            "decoder_forward": (c.c_int, [vp, vp, i32, c.POINTER(vp), i32, vp, vp]),
-            "generate": (c.c_int, [vp, vp, i32, vp, c.POINTER(vp), i32, vp, vp]),
-            "mapping_forward": (c.c_int, [vp, vp, i32, vp, vp]),
-            "generator_forward_w": (c.c_int, [vp, vp, i32, vp, i32, c.POINTER(vp), i32, vp, vp, c.POINTER(vp), i32]),
-            "generate_w": (c.c_int, [vp, vp, i32, vp, i32, c.POINTER(vp), i32, vp, vp]),
-            "generate_downscaled": (c.c_int, [vp, vp, i32, vp, vp, i32, c.POINTER(vp), i32, i32, vp, vp]),
-            "set_overlap": (c.c_int, [vp, i32]),
-            "set_precision": (c.c_int, [vp, i32]),
-            "segmentation_eval": (c.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-            "fill_inputs": (c.c_int, [vp, vp, i32, c.c_uint64, c.c_uint64, vp, c.POINTER(vp), i32]),
-            "profile_enable": (c.c_int, [vp, i32]),
-            "profile_collect": (c.c_int, [vp]),
-            "profile_entry": (c.c_int, [vp, i32, c.POINTER(c.c_char_p), c.POINTER(c.c_double),
-                                        c.POINTER(c.c_int64), c.POINTER(c.c_double),
-                                        c.POINTER(c.c_double), c.POINTER(c.c_double)]),
-            "profile_reset": (c.c_int, [vp]),
-            "version": (c.c_char_p, []),
-            "check": (c.c_int, [vp]),
-            "status_snapshot": (c.c_int, [vp, vp, vp]),
-            "debug_inject": (c.c_int, [vp, i32, i32]),
-        }
-        for name, (res, args) in sig.items():
-            try:
-                fn = getattr(self.lib, prefix + name)
-            except AttributeError:
-                if name in optional:
-                    continue
-                raise GsaError("%s does not export %s%s" % (path, prefix, name))
-            fn.restype = res
-            fn.argtypes = args
-            setattr(self, name, fn)
+        self._fns = {}
+        for header, group in SIGNATURES.items():
+            for name, (res, args) in group.items():
+                try:
+                    fn = getattr(self.lib, name)
+                except AttributeError:
+                    raise GsaError("%s does not export %s" % (path, name))
+                fn.restype = res
+                fn.argtypes = args
+                self._fns[name] = fn
+                if header == "gsa.h":
+                    setattr(self, name[len(prefix):], fn)
+
+    def fn(self, name):
+        """The bound entry ``name`` (full name, e.g. "gsa_mask_morph")."""
+        return self._fns[name]
 
 
 _hip_api = None

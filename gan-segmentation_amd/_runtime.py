@@ -15,6 +15,24 @@ def current_stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def is_device_tensor(t, dtype, dims=None, shape=None, device=None):
+    """Whether ``t`` is a torch tensor on a GPU, of ``dtype`` and contiguous -- and, where given, with one of the dimension counts
+    ``dims``, of ``shape`` and on ``device``.  What every wrapper of a stateless entry asks of a tensor before it passes its address."""
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+            and (dims is None or t.dim() in dims) and (shape is None or tuple(t.shape) == tuple(shape))
+            and (device is None or t.device == device))
+
+
+def launch(name, dev, *args):
+    """Call the stateless entry ``name`` (a row of ``_lib.SIGNATURES`` whose first argument is the stream) with ``args`` behind the
+    current stream of ``dev``.  The C ABI has no context: its kernels go to the calling thread's current device, so ``dev`` is made
+    that for the call.  GsaError on a non-zero status."""
+    with torch.cuda.device(dev):
+        rc = _lib.load_library().fn(name)(current_stream_ptr(dev), *args)
+    if rc != 0:
+        raise _lib.GsaError("%s failed (%d)" % (name, rc))
+
+
 def to_device_f32(x, device):
     """numpy / torch (any device) -> contiguous fp32 torch tensor on ``device``."""
     if isinstance(x, np.ndarray):

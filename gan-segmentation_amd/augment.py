@@ -35,11 +35,9 @@ Mode ``"center"`` takes no draw: steps 4 and 5 only, with the central origin ``o
 The forward map is composed and inverted in float64 and rounded ONCE to fp32: row ``[a b c d e f]`` of the result maps an output
 pixel index to source coordinates, which is what the kernel takes.  All unsigned 64-bit arithmetic wraps modulo 2**64.
 """
-import ctypes
-
 import numpy as np
 
-from .style_mix import splitmix64
+from .style_mix import uniform_draws
 
 AUGMENT_SEED_XOR = 0x4155474D454E5421
 _M64 = (1 << 64) - 1
@@ -55,14 +53,7 @@ MAX_CHANNELS = 4
 # -- the plan ------------------------------------------------------------------------------------------------------------------
 def uniforms(seed, first_index, n):
     """float64 (n, 7): the draws r_0 .. r_6 of the global samples ``first_index .. first_index+n-1`` (module docstring)."""
-    idx = np.arange(n, dtype=np.uint64) + np.uint64(int(first_index) & _M64)
-    u = splitmix64(np.uint64((int(seed) & _M64) ^ AUGMENT_SEED_XOR) ^ idx)
-    out = np.empty((n, NUM_DRAWS), np.float64)
-    for k in range(NUM_DRAWS):
-        if k:
-            u = splitmix64(u)
-        out[:, k] = (u >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
-    return out
+    return uniform_draws(seed, AUGMENT_SEED_XOR, first_index, n, NUM_DRAWS)
 
 
 def check_crop(crop):
@@ -216,35 +207,13 @@ def check_shapes(H, W, channels, out_size):
 
 
 # -- the kernel ----------------------------------------------------------------------------------------------------------------
-_FUNCS = None
-
-
-def _api():
-    global _FUNCS
-    if _FUNCS is None:
-        from . import _lib
-        lib = _lib.load_library().lib
-        c = ctypes
-        vp, i32 = c.c_void_p, c.c_int32
-        sig = {
-            "gsa_augment_pairs": (c.c_int, [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
-        }
-        _FUNCS = {}
-        for name, (res, args) in sig.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-            _FUNCS[name] = fn
-    return _FUNCS
-
-
 def augment_pairs(img, mask, matrices, out_size, scale=None, bias=None, dtype=None, ignore_label=IGNORE_LABEL):
     """img (n, H, W, C) u8 and mask (n, H, W) u8 device tensors (what ``ImageGenerator.generate_batch`` returns), matrices (n, 6)
     fp32 (a device tensor, or a numpy array that is uploaded) -> (image (n, C, out_h, out_w) ``dtype``, label (n, out_h, out_w) u8):
     new device tensors, enqueued on the current stream.  ``scale``, ``bias``: per-channel floats (``normalisation``; default: the
     ImageNet statistics, three channels); ``dtype``: torch.float32 (default) or torch.bfloat16."""
     import torch
-    from . import _lib
-    from ._runtime import current_stream_ptr
+    from ._runtime import is_device_tensor, launch
     dtype = torch.float32 if dtype is None else dtype
     if dtype not in (torch.float32, torch.bfloat16):
         raise ValueError("dtype must be torch.float32 or torch.bfloat16, got %r" % (dtype,))
@@ -260,22 +229,17 @@ def augment_pairs(img, mask, matrices, out_size, scale=None, bias=None, dtype=No
     if len(scale) != C or len(bias) != C:
         raise ValueError("scale and bias need one value per channel (%d), got %d and %d" % (C, len(scale), len(bias)))
     for t in (img, mask):
-        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or t.device != img.device:
+        if not is_device_tensor(t, torch.uint8, device=img.device):
             raise ValueError("augment_pairs takes contiguous uint8 tensors on one GPU")
     dev = img.device
     if isinstance(matrices, np.ndarray):
         # through pinned memory, so that the upload is stream-ordered and the host does not wait for the batch in front of it
         matrices = torch.from_numpy(np.ascontiguousarray(matrices, np.float32)).pin_memory().to(dev, non_blocking=True)
-    if (tuple(matrices.shape) != (n, 6) or matrices.dtype != torch.float32 or matrices.device != dev or not matrices.is_contiguous()):
+    if not is_device_tensor(matrices, torch.float32, shape=(n, 6), device=dev):
         raise ValueError("matrices must be a contiguous float32 (%d, 6) tensor on %s" % (n, dev))
-    with torch.cuda.device(dev):        # the C ABI is stateless: the kernel goes to the calling thread's current device
-        image = torch.empty((n, C, oh, ow), dtype=dtype, device=dev)
-        label = torch.empty((n, oh, ow), dtype=torch.uint8, device=dev)
-        if n == 0:
-            return image, label
-        rc = _api()["gsa_augment_pairs"](current_stream_ptr(dev), n, H, W, C, img.data_ptr(), mask.data_ptr(), matrices.data_ptr(),
-                                         scale.ctypes.data, bias.ctypes.data, oh, ow, 1 if dtype == torch.bfloat16 else 0,
-                                         int(ignore_label), image.data_ptr(), label.data_ptr())
-    if rc != 0:
-        raise _lib.GsaError("gsa_augment_pairs failed (%d)" % rc)
+    image = torch.empty((n, C, oh, ow), dtype=dtype, device=dev)
+    label = torch.empty((n, oh, ow), dtype=torch.uint8, device=dev)
+    if n:
+        launch("gsa_augment_pairs", dev, n, H, W, C, img.data_ptr(), mask.data_ptr(), matrices.data_ptr(), scale.ctypes.data,
+               bias.ctypes.data, oh, ow, 1 if dtype == torch.bfloat16 else 0, int(ignore_label), image.data_ptr(), label.data_ptr())
     return image, label

@@ -220,9 +220,9 @@ class DatasetWriter:
         enc = self._encoders[slot].get(kind)
         if enc is None or enc.n < n or (enc.H, enc.W) != (H, W) or enc.device != device:
             if kind == "jpeg":
-                from . import jpeg
+                from . import _lib, jpeg
                 kw = {} if self.jpeg_restart is None else {"restart": self.jpeg_restart}
-                worst = jpeg._api()["gsa_jpeg_max_scan_bytes"](H, W, kw.get("restart", jpeg.DEFAULT_RESTART))
+                worst = _lib.load_library().fn("gsa_jpeg_max_scan_bytes")(H, W, kw.get("restart", jpeg.DEFAULT_RESTART))
                 enc = jpeg.JpegEncoder(n, H, W, device, quality=self.jpeg_quality, out_stride=worst, **kw)
             else:
                 from . import png

@@ -39,7 +39,7 @@ from . import mask_ops as _mask_ops
 from . import photometric as _photometric
 from . import style_mix as _style_mix
 from . import weights as _weights
-from ._runtime import current_stream_ptr, split_sizes, to_device_f32
+from ._runtime import current_stream_ptr, is_device_tensor, split_sizes, to_device_f32
 from .dataset_writer import STATUS_RING_DEPTH
 from .networks_seg import Decoder
 from .networks_stylegan import Generator
@@ -55,36 +55,9 @@ class ImageGenerator:
 
     def __init__(self, gpu_ids, gan_dir, gan="ffhq", batch_size=4, return_latents=False, seed=0, precision="fp32",
                  truncation_psi=None, style_mix_prob=0.0, output_downscale=1, mask_morph=False):
-        max_res_log2_dict = _weights.GAN_MAX_RES_LOG2
-        self.max_res_log2 = max_res_log2_dict[gan]
-        self.output_downscale = self.check_output_downscale(output_downscale, self.max_res_log2)
-        self.mask_morph = self.check_mask_morph(mask_morph)
-        self.latent_size = 512
-        self.return_latents = return_latents
-        self.batch_size = batch_size
-        gpu_ids = list(gpu_ids)
-        if len(gpu_ids) == 0:
-            raise RuntimeError("the MI355X path has no CPU context: pass at least one gpu id "
-                               "(the reference falls back to mx.cpu(), image_generator.py:17)")
-        self.ctx = gpu_ids      # the reference's device list (image_generator.py:17): one weight replica per entry
-        self.precision = precision
-        self.style_mix_prob = self._check_mix_prob(style_mix_prob)
-        self.cfg = self._get_config(max_res_log2=self.max_res_log2)
-        stylegan_name = "stylegan-%s.params" % gan
-        from . import params as _params
-        tensors = _params.load_params(os.path.join(gan_dir, stylegan_name))     # read once, loaded into every replica
-        self._gens = []
-        for dev in gpu_ids:
-            g = self._get_G(self.cfg, dev)
-            g.load_parameters(tensors, ignore_extra=True, truncation_psi=truncation_psi)
-            self._gens.append(g)
-        self.netG = self._gens[0]
-        self._decoder = None
-        self._decoders = []
-        self._rng = torch.Generator(device="cpu")
-        self._rng.manual_seed(seed)
-        for g in self._gens:
-            g.seed(seed)
+        cfg = self._get_config(max_res_log2=_weights.GAN_MAX_RES_LOG2[gan])
+        self._setup(cfg, os.path.join(gan_dir, "stylegan-%s.params" % gan), gpu_ids, batch_size, return_latents, seed, precision,
+                    truncation_psi, style_mix_prob, output_downscale, mask_morph)
 
     @classmethod
     def from_params(cls, gcfg, gparams, dcfg=None, dparams=None, gpu_ids=(0,), batch_size=4,
@@ -92,31 +65,44 @@ class ImageGenerator:
                     mask_morph=False):
         """Build from in-memory weights (tests, benchmarks: no pretrained files exist here)."""
         self = cls.__new__(cls)
-        self.max_res_log2 = gcfg["max_res_log2"]
-        self.output_downscale = cls.check_output_downscale(output_downscale, self.max_res_log2)
-        self.mask_morph = cls.check_mask_morph(mask_morph)
-        self.latent_size = gcfg["latent_size"]
+        self._setup(dict(gcfg), gparams, gpu_ids, batch_size, return_latents, seed, precision, truncation_psi, style_mix_prob,
+                    output_downscale, mask_morph)
+        if dcfg is not None:
+            self.attach_decoder(dcfg, dparams)
+        return self
+
+    def _setup(self, cfg, gparams, gpu_ids, batch_size, return_latents, seed, precision, truncation_psi, style_mix_prob,
+               output_downscale, mask_morph):
+        """What both constructors do: the options, checked before any file or device is touched; one generator replica per gpu
+        id, loaded from ``gparams`` (a ``.params`` path, read once, or a ``{name: array}`` dict); the seeds."""
+        self.cfg = cfg
+        self.max_res_log2 = cfg["max_res_log2"]
+        self.output_downscale = self.check_output_downscale(output_downscale, self.max_res_log2)
+        self.mask_morph = self.check_mask_morph(mask_morph)
+        self.latent_size = cfg["latent_size"]
         self.return_latents = return_latents
         self.batch_size = batch_size
-        self.ctx = list(gpu_ids)
-        self.cfg = dict(gcfg)
+        self.ctx = list(gpu_ids)      # the reference's device list (image_generator.py:17): one weight replica per entry
+        if len(self.ctx) == 0:
+            raise RuntimeError("the MI355X path has no CPU context: pass at least one gpu id "
+                               "(the reference falls back to mx.cpu(), image_generator.py:17)")
         self.precision = precision
-        self.style_mix_prob = cls._check_mix_prob(style_mix_prob)
+        self.style_mix_prob = self._check_mix_prob(style_mix_prob)
+        if isinstance(gparams, (str, bytes)):
+            from . import params as _params
+            gparams = _params.load_params(gparams)
         self._gens = []
         for dev in self.ctx:
-            g = Generator(self.cfg, device=dev, precision=precision)
-            g.load_parameters(gparams, truncation_psi=truncation_psi)
+            g = self._get_G(self.cfg, dev)
+            g.load_parameters(gparams, ignore_extra=True, truncation_psi=truncation_psi)
             self._gens.append(g)
         self.netG = self._gens[0]
         self._decoder = None
         self._decoders = []
-        if dcfg is not None:
-            self.attach_decoder(dcfg, dparams)
         self._rng = torch.Generator(device="cpu")
         self._rng.manual_seed(seed)
         for g in self._gens:
             g.seed(seed)
-        return self
 
     @staticmethod
     def _check_mix_prob(p):
@@ -335,26 +321,30 @@ class ImageGenerator:
         R, nc = 2 ** self.max_res_log2 // self.output_downscale, self.netG.nc
         img, mask = out
         for t, shape in ((img, (n, R, R, nc)), (mask, (n, R, R))):
-            if tuple(t.shape) != shape or t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
+            if not is_device_tensor(t, torch.uint8, shape=shape, device=dev):
                 raise ValueError("out tensors must be contiguous uint8 %s on %s" % (shape, dev))
         return img, mask
+
+    def _pair_buffers(self, r, n, out):
+        """(img, raw mask, final mask) of a fused step of ``n`` samples on replica ``r``: new tensors, or the checked ``out``; the
+        step writes the raw mask, ``_finish_mask`` turns it into the final one (the same tensor without ``mask_morph``)."""
+        g = self._gens[r]
+        dev = g._model.device
+        if out is None:
+            R = 2 ** self.max_res_log2 // self.output_downscale
+            img = torch.empty((n, R, R, g.nc), device=dev, dtype=torch.uint8)
+            mask = torch.empty((n, R, R), device=dev, dtype=torch.uint8)
+        else:
+            img, mask = self._check_out(out, n, dev)
+        return img, self._raw_mask(r, mask), mask
 
     def _generate_on(self, r, z, noise, out=None):
         """The fused step on replica ``r`` (its own device and stream)."""
         g = self._gens[r]
         z, noise, n = g._prepare(z, noise)
-        model = g._model
-        dev = model.device
-        R = 2 ** self.max_res_log2 // self.output_downscale
-        if out is None:
-            img = torch.empty((n, R, R, g.nc), device=dev, dtype=torch.uint8)
-            mask = torch.empty((n, R, R), device=dev, dtype=torch.uint8)
-        else:
-            img, mask = self._check_out(out, n, dev)
-        nptrs = [a.data_ptr() for a in noise]
-        final, mask = mask, self._raw_mask(r, mask)
-        self._run_step(model, dev, n, z, nptrs, img, mask)
-        return img, self._finish_mask(mask, final)
+        img, raw, final = self._pair_buffers(r, n, out)
+        self._run_step(g._model, g._model.device, n, z, [a.data_ptr() for a in noise], img, raw)
+        return img, self._finish_mask(raw, final)
 
     def _raw_mask(self, r, mask):
         """Where the step of replica ``r`` writes its mask: ``mask`` itself, or with ``mask_morph`` a scratch tensor kept per replica,
@@ -412,32 +402,26 @@ class ImageGenerator:
         self._step(model.ctx, current_stream_ptr(dev), n, z, nptrs, img, mask, self.output_downscale)
 
     @staticmethod
-    def _step(ctx, stream, n, z, nptrs, img, mask, factor):
-        """One fused z step: gsa_generate, or gsa_generate_downscaled when the pair is written at 1/factor resolution."""
-        if factor == 1:
-            ctx.generate(stream, n, z.data_ptr(), nptrs, img.data_ptr(), mask.data_ptr())
+    def _step(ctx, stream, n, z, nptrs, img, mask, factor, dlatents=None, num_layers=0):
+        """One fused step from ``z`` or (``z`` None) from per-layer ``dlatents``: gsa_generate / gsa_generate_w, or
+        gsa_generate_downscaled when the pair is written at 1/factor resolution.  The one place that chooses the entry."""
+        zp = None if z is None else z.data_ptr()
+        dp = None if dlatents is None else dlatents.data_ptr()
+        if factor != 1:
+            ctx.generate_downscaled(stream, n, zp, dp, num_layers, nptrs, factor, img.data_ptr(), mask.data_ptr())
+        elif dlatents is None:
+            ctx.generate(stream, n, zp, nptrs, img.data_ptr(), mask.data_ptr())
         else:
-            ctx.generate_downscaled(stream, n, z.data_ptr(), None, 0, nptrs, factor, img.data_ptr(), mask.data_ptr())
+            ctx.generate_w(stream, n, dp, num_layers, nptrs, img.data_ptr(), mask.data_ptr())
 
     def _generate_on_w(self, r, dlatents, noise, out=None):
         """The fused step from per-layer dlatents on replica ``r`` (gsa_generate_w); always eager."""
         g = self._gens[r]
         dl, noise, n = g._prepare_w(dlatents, noise)
-        dev = g._model.device
-        R = 2 ** self.max_res_log2 // self.output_downscale
-        if out is None:
-            img = torch.empty((n, R, R, g.nc), device=dev, dtype=torch.uint8)
-            mask = torch.empty((n, R, R), device=dev, dtype=torch.uint8)
-        else:
-            img, mask = self._check_out(out, n, dev)
-        nptrs = [a.data_ptr() for a in noise]
-        final, mask = mask, self._raw_mask(r, mask)
-        if self.output_downscale == 1:
-            g._model.ctx.generate_w(current_stream_ptr(dev), n, dl.data_ptr(), g.num_style_layers, nptrs, img.data_ptr(), mask.data_ptr())
-        else:
-            g._model.ctx.generate_downscaled(current_stream_ptr(dev), n, None, dl.data_ptr(), g.num_style_layers, nptrs,
-                                             self.output_downscale, img.data_ptr(), mask.data_ptr())
-        return img, self._finish_mask(mask, final)
+        img, raw, final = self._pair_buffers(r, n, out)
+        self._step(g._model.ctx, current_stream_ptr(g._model.device), n, None, [a.data_ptr() for a in noise], img, raw,
+                   self.output_downscale, dl, g.num_style_layers)
+        return img, self._finish_mask(raw, final)
 
     @staticmethod
     def _capture(model, dev, n, z, nptrs, img, mask, factor=1):
@@ -531,33 +515,29 @@ class ImageGenerator:
             return oi, om
         return img, mask
 
+    def _generate_split(self, on, x, noise, out):
+        """``on`` (``_generate_on`` or ``_generate_on_w``) of the batch ``x``: on the one replica, or split over the replicas like
+        the reference's ``split_and_load`` and collected on the first device."""
+        if self._decoder is None:
+            raise RuntimeError("attach_decoder() first")
+        if len(self._gens) == 1:
+            return on(0, x, noise, out)
+        n = len(x)
+        parts = []
+        for r, lo, hi in split_sizes(n, len(self._gens)):
+            with torch.cuda.device(self._gens[r]._model.device):
+                parts.append(on(r, x[lo:hi], None if noise is None else [a[lo:hi] for a in noise]))
+        return self._collect(parts, n, out)
+
     def generate_batch(self, z, noise=None, out=None):
         """latents (N,512) [+ noise planes] -> (img (N,R,R,3) u8, mask (N,R,R) u8) on the GPU (R/f with output_downscale f).
         The per-batch body of ``main.py generate`` (reference main.py:97-99) in one call.
         ``out=(img, mask)``: write into these contiguous uint8 device tensors instead of new ones
         (e.g. the fused send buffer of ``dist.PairGatherer``).  With several gpu ids the batch is split over the
         replicas like the reference's ``split_and_load`` and the pairs are collected on the first device."""
-        if self._decoder is None:
-            raise RuntimeError("attach_decoder() first")
-        if len(self._gens) == 1:
-            return self._generate_on(0, z, noise, out)
-        n = len(z)
-        parts = []
-        for r, lo, hi in split_sizes(n, len(self._gens)):
-            with torch.cuda.device(self._gens[r]._model.device):
-                parts.append(self._generate_on(r, z[lo:hi], None if noise is None else [a[lo:hi] for a in noise]))
-        return self._collect(parts, n, out)
+        return self._generate_split(self._generate_on, z, noise, out)
 
     def generate_batch_w(self, dlatents, noise=None, out=None):
         """``generate_batch`` from per-layer latents: dlatents (N, L, 512), untruncated (the loaded ``truncation_psi`` is
         applied per layer), L = 2*(max_res_log2-1).  Split over the replicas like ``generate_batch``; eager (no hipGraph)."""
-        if self._decoder is None:
-            raise RuntimeError("attach_decoder() first")
-        if len(self._gens) == 1:
-            return self._generate_on_w(0, dlatents, noise, out)
-        n = len(dlatents)
-        parts = []
-        for r, lo, hi in split_sizes(n, len(self._gens)):
-            with torch.cuda.device(self._gens[r]._model.device):
-                parts.append(self._generate_on_w(r, dlatents[lo:hi], None if noise is None else [a[lo:hi] for a in noise]))
-        return self._collect(parts, n, out)
+        return self._generate_split(self._generate_on_w, dlatents, noise, out)

@@ -12,39 +12,17 @@ import ctypes
 import torch
 
 from . import _lib
-from ._runtime import current_stream_ptr
-
-_FUNCS = None
+from ._runtime import current_stream_ptr, is_device_tensor, launch
 
 DEFAULT_QUALITY = 95     # cv2.imwrite's default JPEG quality (the reference passes none)
 DEFAULT_RESTART = 4      # MCUs (16x16 px) per restart interval = one wave of the entropy-coding kernel: 1024 independent
 #                          waves per 1024^2 image, +0.25 % bytes; measured on 8 FFHQ-size images: 0.09 ms for restart 1, 2 or 4
 
 
-def _api():
-    global _FUNCS
-    if _FUNCS is None:
-        lib = _lib.load_library().lib
-        c = ctypes
-        vp, i32, i64 = c.c_void_p, c.c_int32, c.c_int64
-        sig = {
-            "gsa_jpeg_header": (i64, [i32, i32, i32, i32, vp, i64]),
-            "gsa_jpeg_workspace_bytes": (i64, [i32, i32, i32, i32]),
-            "gsa_jpeg_max_scan_bytes": (i64, [i32, i32, i32]),
-            "gsa_jpeg_encode": (c.c_int, [vp, i32, i32, i32, vp, i32, i32, vp, i64, vp, i64, vp]),
-        }
-        _FUNCS = {}
-        for name, (res, args) in sig.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-            _FUNCS[name] = fn
-    return _FUNCS
-
-
 def header(H, W, quality=DEFAULT_QUALITY, restart=DEFAULT_RESTART):
     """The bytes in front of the entropy-coded data (SOI .. SOS), host side."""
     buf = ctypes.create_string_buffer(1024)
-    n = _api()["gsa_jpeg_header"](H, W, quality, restart, ctypes.cast(buf, ctypes.c_void_p), 1024)
+    n = _lib.load_library().fn("gsa_jpeg_header")(H, W, quality, restart, ctypes.cast(buf, ctypes.c_void_p), 1024)
     if n < 0 or n > 1024:
         raise _lib.GsaError("gsa_jpeg_header failed (%d)" % n)
     return buf.raw[:n]
@@ -52,11 +30,11 @@ def header(H, W, quality=DEFAULT_QUALITY, restart=DEFAULT_RESTART):
 
 class JpegEncoder:
     def __init__(self, n, H, W, device, quality=DEFAULT_QUALITY, restart=DEFAULT_RESTART, out_stride=None):
-        api = _api()
+        fn = _lib.load_library().fn
         self.n, self.H, self.W, self.quality, self.restart = n, H, W, quality, restart
         self.device = torch.device(device)
-        ws = api["gsa_jpeg_workspace_bytes"](n, H, W, restart)
-        worst = api["gsa_jpeg_max_scan_bytes"](H, W, restart)
+        ws = fn("gsa_jpeg_workspace_bytes")(n, H, W, restart)
+        worst = fn("gsa_jpeg_max_scan_bytes")(H, W, restart)
         if ws < 0 or worst < 0:
             raise ValueError("JPEG encoder: images must be multiples of 16 px (got %dx%d), restart in 1..65535; other "
                              "sizes go through the host encoder (DatasetWriter(gpu_jpeg=False) / JPEG_ON_GPU: false)" % (H, W))
@@ -74,17 +52,13 @@ class JpegEncoder:
 
     def encode(self, img):
         """img: (k, H, W, 3) uint8 CUDA tensor, k <= n.  -> (scan (k, stride) u8, lengths (k,) i32), stream-ordered."""
-        if not img.is_cuda or img.dtype != torch.uint8 or not img.is_contiguous():
+        if not is_device_tensor(img, torch.uint8):
             raise ValueError("encode takes a contiguous uint8 CUDA tensor")
         k = img.shape[0]
         if k > self.n or tuple(img.shape[1:]) != (self.H, self.W, 3):
             raise ValueError("image batch %s does not fit the encoder (%d, %d, %d, 3)" % (tuple(img.shape), self.n, self.H, self.W))
-        with torch.cuda.device(img.device):     # the C ABI is stateless: kernels go to the calling thread's current device
-            rc = _api()["gsa_jpeg_encode"](current_stream_ptr(img.device), k, self.H, self.W, img.data_ptr(), self.quality,
-                                           self.restart, self._ws.data_ptr(), self._ws.numel(), self.out.data_ptr(),
-                                           self.out_stride, self.lengths.data_ptr())
-        if rc != 0:
-            raise _lib.GsaError("gsa_jpeg_encode failed (%d)" % rc)
+        launch("gsa_jpeg_encode", img.device, k, self.H, self.W, img.data_ptr(), self.quality, self.restart, self._ws.data_ptr(),
+               self._ws.numel(), self.out.data_ptr(), self.out_stride, self.lengths.data_ptr())
         return self.out[:k], self.lengths[:k]
 
     def grow(self):
@@ -105,27 +79,8 @@ class JpegEncoder:
 
 
 # -- the round trip (include/gsa_jpeg_roundtrip.h) -------------------------------------------------------------------------------
-_ROUNDTRIP_FUNCS = None
 _ROUNDTRIP_WORKSPACES = {}       # (device index, stream, bytes) -> u8 tensor; a handful of sizes per process
 _ROUNDTRIP_WORKSPACES_MAX = 8
-
-
-def _roundtrip_api():
-    global _ROUNDTRIP_FUNCS
-    if _ROUNDTRIP_FUNCS is None:
-        lib = _lib.load_library().lib
-        c = ctypes
-        vp, i32, i64 = c.c_void_p, c.c_int32, c.c_int64
-        sig = {
-            "gsa_jpeg_roundtrip_workspace_bytes": (i64, [i32, i32, i32]),
-            "gsa_jpeg_roundtrip": (c.c_int, [vp, i32, i32, i32, vp, i32, vp, i64, vp]),
-        }
-        _ROUNDTRIP_FUNCS = {}
-        for name, (res, args) in sig.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-            _ROUNDTRIP_FUNCS[name] = fn
-    return _ROUNDTRIP_FUNCS
 
 
 def check_quality(quality, what="quality"):
@@ -150,32 +105,26 @@ def roundtrip(img, quality=DEFAULT_QUALITY, out=None):
     a reader of ``JpegEncoder``'s files sees.  Enqueued on the current stream of ``img``'s device; the workspace (1.5 bytes per
     pixel) is cached per device, stream and size.  No CPU fallback."""
     quality = check_quality(quality)
-    if not isinstance(img, torch.Tensor) or img.dim() != 4 or not img.is_cuda or img.dtype != torch.uint8 or not img.is_contiguous():
+    if not is_device_tensor(img, torch.uint8, dims=(4,)):
         raise ValueError("roundtrip takes a contiguous uint8 CUDA tensor (n, H, W, 3)")
     n, H, W, C = img.shape
     check_roundtrip_shape(H, W, C)
     dev = img.device
     if out is not None:
-        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(img.shape) or out.dtype != torch.uint8 or out.device != dev
-                or not out.is_contiguous() or (n and out.data_ptr() == img.data_ptr())):
+        if not is_device_tensor(out, torch.uint8, shape=img.shape, device=dev) or (n and out.data_ptr() == img.data_ptr()):
             raise ValueError("out must be another contiguous uint8 tensor %s on %s" % (tuple(img.shape), dev))
-    api = _roundtrip_api()
-    with torch.cuda.device(dev):        # the C ABI is stateless: the kernels go to the calling thread's current device
-        if out is None:
-            out = torch.empty_like(img)
-        if n == 0:
-            return out
-        need = api["gsa_jpeg_roundtrip_workspace_bytes"](n, H, W)
-        if need < 0:
-            raise _lib.GsaError("gsa_jpeg_roundtrip_workspace_bytes failed (%d)" % need)
-        stream = current_stream_ptr(dev)
-        key = (dev.index, stream, need)
-        ws = _ROUNDTRIP_WORKSPACES.get(key)
-        if ws is None:
-            if len(_ROUNDTRIP_WORKSPACES) >= _ROUNDTRIP_WORKSPACES_MAX:
-                _ROUNDTRIP_WORKSPACES.pop(next(iter(_ROUNDTRIP_WORKSPACES)))
-            ws = _ROUNDTRIP_WORKSPACES[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-        rc = api["gsa_jpeg_roundtrip"](stream, n, H, W, img.data_ptr(), quality, ws.data_ptr(), ws.numel(), out.data_ptr())
-    if rc != 0:
-        raise _lib.GsaError("gsa_jpeg_roundtrip failed (%d)" % rc)
+    if out is None:
+        out = torch.empty_like(img)
+    if n == 0:
+        return out
+    need = _lib.load_library().fn("gsa_jpeg_roundtrip_workspace_bytes")(n, H, W)
+    if need < 0:
+        raise _lib.GsaError("gsa_jpeg_roundtrip_workspace_bytes failed (%d)" % need)
+    key = (dev.index, current_stream_ptr(dev), need)
+    ws = _ROUNDTRIP_WORKSPACES.get(key)
+    if ws is None:
+        if len(_ROUNDTRIP_WORKSPACES) >= _ROUNDTRIP_WORKSPACES_MAX:
+            _ROUNDTRIP_WORKSPACES.pop(next(iter(_ROUNDTRIP_WORKSPACES)))
+        ws = _ROUNDTRIP_WORKSPACES[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    launch("gsa_jpeg_roundtrip", dev, n, H, W, img.data_ptr(), quality, ws.data_ptr(), ws.numel(), out.data_ptr())
     return out

@@ -3,38 +3,15 @@ counterpart of reference utils.morph_mask (utils.py:105-109): a 5x5 close follow
 
 ``morph_mask(mask)`` enqueues one kernel on the current stream of ``mask``'s device and returns the cleaned mask;
 ``ImageGenerator(..., mask_morph=True)`` applies it to the mask of every fused call.  No CPU fallback."""
-import ctypes
-
 import torch
 
-from . import _lib
-from ._runtime import current_stream_ptr
-
-_FUNCS = None
+from ._runtime import is_device_tensor, launch
 
 MAX_EXTENT = 65535
 
 
-def _api():
-    global _FUNCS
-    if _FUNCS is None:
-        lib = _lib.load_library().lib
-        c = ctypes
-        vp, i32 = c.c_void_p, c.c_int32
-        sig = {
-            "gsa_mask_morph": (c.c_int, [vp, i32, i32, i32, vp, vp]),
-        }
-        _FUNCS = {}
-        for name, (res, args) in sig.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-            _FUNCS[name] = fn
-    return _FUNCS
-
-
 def _check(t, what):
-    if (not isinstance(t, torch.Tensor) or t.dim() not in (2, 3) or not t.is_cuda or t.dtype != torch.uint8
-            or not t.is_contiguous()):
+    if not is_device_tensor(t, torch.uint8, dims=(2, 3)):
         raise ValueError("%s must be a contiguous uint8 CUDA tensor (H, W) or (n, H, W)" % what)
 
 
@@ -56,12 +33,8 @@ def morph_mask(mask, out=None):
         a, b, size = mask.data_ptr(), out.data_ptr(), mask.numel()
         if out is mask or (size and a < b + size and b < a + size):
             raise ValueError("out must not be, or overlap, the input mask")
-    with torch.cuda.device(dev):        # the C ABI is stateless: the kernel goes to the calling thread's current device
-        if out is None:
-            out = torch.empty_like(mask)
-        if n == 0:
-            return out
-        rc = _api()["gsa_mask_morph"](current_stream_ptr(dev), n, H, W, mask.data_ptr(), out.data_ptr())
-    if rc != 0:
-        raise _lib.GsaError("gsa_mask_morph failed (%d)" % rc)
+    if out is None:
+        out = torch.empty_like(mask)
+    if n:
+        launch("gsa_mask_morph", dev, n, H, W, mask.data_ptr(), out.data_ptr())
     return out

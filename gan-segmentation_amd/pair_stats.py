@@ -7,7 +7,6 @@ per channel the sum of squares, and the two edge counts -- all integers, so the 
 and number of ranks.  ``unpack`` names the fields, ``summarise`` turns the rows of a dataset into the report a consumer needs
 (class frequencies and weights, Normalize constants, empty masks), ``DatasetWriter(stats=True)`` collects them while `generate`
 writes, and ``python -m gan_segmentation_amd.pair_stats DIR`` merges the shard files of a run.  No CPU fallback for the pass."""
-import ctypes
 import glob
 import json
 import os
@@ -30,27 +29,6 @@ FIELDS = {
 SHARD_FORMAT = "pair_stats_%06d_%06d.npz"
 SUMMARY_NAME = "pair_stats_summary.json"
 
-_FUNCS = None
-
-
-def _api():
-    global _FUNCS
-    if _FUNCS is None:
-        from . import _lib
-        lib = _lib.load_library().lib
-        c = ctypes
-        vp, i32 = c.c_void_p, c.c_int32
-        sig = {
-            "gsa_pair_stats": (c.c_int, [vp, i32, i32, i32, i32, vp, vp, vp]),
-        }
-        _FUNCS = {}
-        for name, (res, args) in sig.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-            _FUNCS[name] = fn
-    return _FUNCS
-
-
 def check_pair_stats(v):
     """The PAIR_STATS switch: a real bool (ValueError otherwise -- 1, "yes" or None are not an answer)."""
     if not isinstance(v, bool):
@@ -64,12 +42,10 @@ def pair_stats(img, mask, out=None):
     (new, or ``out``, every word of which is overwritten): the rows of include/gsa_stats.h.  Enqueued on the current stream of the
     mask's device, no synchronisation; the inputs are not written.  ValueError on anything else; no CPU fallback."""
     import torch
-    from . import _lib
-    from ._runtime import current_stream_ptr
+    from ._runtime import is_device_tensor, launch
 
     def u8(t, dims, what):
-        if (not isinstance(t, torch.Tensor) or t.dim() not in dims or not t.is_cuda or t.dtype != torch.uint8
-                or not t.is_contiguous()):
+        if not is_device_tensor(t, torch.uint8, dims=dims):
             raise ValueError("%s must be a contiguous uint8 CUDA tensor with %s dimensions" % (what, " or ".join(map(str, dims))))
 
     u8(mask, (2, 3), "mask")
@@ -85,19 +61,12 @@ def pair_stats(img, mask, out=None):
     if not 1 <= H <= MAX_EXTENT or not 1 <= W <= MAX_EXTENT or H * W >= 2 ** 31:
         raise ValueError("pair_stats takes planes whose sides are 1..%d px with fewer than 2^31 pixels, got %dx%d" % (MAX_EXTENT, H, W))
     dev = mask.device
-    if out is not None:
-        if (not isinstance(out, torch.Tensor) or out.dtype != torch.int64 or tuple(out.shape) != (n, ROW) or out.device != dev
-                or not out.is_contiguous()):
-            raise ValueError("out must be a contiguous int64 tensor (%d, %d) on %s" % (n, ROW, dev))
-    with torch.cuda.device(dev):        # the C ABI is stateless: the kernels go to the calling thread's current device
-        if out is None:
-            out = torch.empty((n, ROW), dtype=torch.int64, device=dev)
-        if n == 0:
-            return out
-        rc = _api()["gsa_pair_stats"](current_stream_ptr(dev), n, H, W, C, img.data_ptr() if C else None, mask.data_ptr(),
-                                      out.data_ptr())
-    if rc != 0:
-        raise _lib.GsaError("gsa_pair_stats failed (%d)" % rc)
+    if out is not None and not is_device_tensor(out, torch.int64, shape=(n, ROW), device=dev):
+        raise ValueError("out must be a contiguous int64 tensor (%d, %d) on %s" % (n, ROW, dev))
+    if out is None:
+        out = torch.empty((n, ROW), dtype=torch.int64, device=dev)
+    if n:
+        launch("gsa_pair_stats", dev, n, H, W, C, img.data_ptr() if C else None, mask.data_ptr(), out.data_ptr())
     return out
 
 

@@ -24,11 +24,9 @@ device never sees a denormal product), normalised to sum 1, rounded ONCE to fp32
 A row of the plan is ``alpha, offset[0..3], noise, w[0..6], 0, 0, 0``: 16 fp32 values.  With every limit zero the rows make the kernel
 the identity.  All unsigned 64-bit arithmetic wraps modulo 2**64.
 """
-import ctypes
-
 import numpy as np
 
-from .style_mix import splitmix64
+from .style_mix import uniform_draws
 
 PHOTOMETRIC_SEED_XOR = 0x50484F544F4D4554
 _M64 = (1 << 64) - 1
@@ -46,14 +44,7 @@ ZERO_LIMITS = {k: 0.0 for k in DEFAULT_LIMITS}
 # -- the plan ------------------------------------------------------------------------------------------------------------------
 def uniforms(seed, first_index, n):
     """float64 (n, 10): the draws r_0 .. r_9 of the global samples ``first_index .. first_index+n-1`` (module docstring)."""
-    idx = np.arange(n, dtype=np.uint64) + np.uint64(int(first_index) & _M64)
-    u = splitmix64(np.uint64((int(seed) & _M64) ^ PHOTOMETRIC_SEED_XOR) ^ idx)
-    out = np.empty((n, NUM_DRAWS), np.float64)
-    for k in range(NUM_DRAWS):
-        if k:
-            u = splitmix64(u)
-        out[:, k] = (u >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
-    return out
+    return uniform_draws(seed, PHOTOMETRIC_SEED_XOR, first_index, n, NUM_DRAWS)
 
 
 def check_limits(limits):
@@ -147,36 +138,14 @@ def check_shape(H, W, channels):
 
 
 # -- the kernel ----------------------------------------------------------------------------------------------------------------
-_FUNCS = None
-
-
-def _api():
-    global _FUNCS
-    if _FUNCS is None:
-        from . import _lib
-        lib = _lib.load_library().lib
-        c = ctypes
-        vp, i32, u64 = c.c_void_p, c.c_int32, c.c_uint64
-        sig = {
-            "gsa_photometric": (c.c_int, [vp, i32, i32, i32, i32, vp, vp, u64, u64, vp]),
-        }
-        _FUNCS = {}
-        for name, (res, args) in sig.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-            _FUNCS[name] = fn
-    return _FUNCS
-
-
 def photometric(img, params, seed, first_index):
     """img (n, H, W, C) contiguous u8 device tensor (what ``ImageGenerator.generate_indexed`` returns), params (n, 16) fp32 (a
     device tensor, or a numpy array that is uploaded), sample k being the global sample ``first_index + k`` of ``seed`` -> a new
     (n, H, W, C) u8 tensor: the rule of include/gsa_photometric.h, enqueued on the current stream of ``img``'s device.  The input
     is not written.  ValueError on anything else; no CPU fallback."""
     import torch
-    from . import _lib
-    from ._runtime import current_stream_ptr
-    if (not isinstance(img, torch.Tensor) or img.dim() != 4 or not img.is_cuda or img.dtype != torch.uint8 or not img.is_contiguous()):
+    from ._runtime import is_device_tensor, launch
+    if not is_device_tensor(img, torch.uint8, dims=(4,)):
         raise ValueError("photometric takes a contiguous uint8 CUDA tensor (n, H, W, C)")
     n, H, W, C = img.shape
     check_shape(H, W, C)
@@ -186,16 +155,10 @@ def photometric(img, params, seed, first_index):
             raise ValueError("params must be (%d, %d), got %s" % (n, ROW, params.shape))
         # through pinned memory, so that the upload is stream-ordered and the host does not wait for the batch in front of it
         params = torch.from_numpy(np.ascontiguousarray(params, np.float32)).pin_memory().to(dev, non_blocking=True)
-    if (not isinstance(params, torch.Tensor) or tuple(params.shape) != (n, ROW) or params.dtype != torch.float32
-            or params.device != dev or not params.is_contiguous()):
+    if not is_device_tensor(params, torch.float32, shape=(n, ROW), device=dev):
         raise ValueError("params must be a contiguous float32 (%d, %d) tensor on %s" % (n, ROW, dev))
     seed, first_index = int(seed) & _M64, int(first_index) & _M64
-    with torch.cuda.device(dev):        # the C ABI is stateless: the kernel goes to the calling thread's current device
-        out = torch.empty_like(img)
-        if n == 0:
-            return out
-        rc = _api()["gsa_photometric"](current_stream_ptr(dev), n, H, W, C, img.data_ptr(), params.data_ptr(), seed, first_index,
-                                       out.data_ptr())
-    if rc != 0:
-        raise _lib.GsaError("gsa_photometric failed (%d)" % rc)
+    out = torch.empty_like(img)
+    if n:
+        launch("gsa_photometric", dev, n, H, W, C, img.data_ptr(), params.data_ptr(), seed, first_index, out.data_ptr())
     return out

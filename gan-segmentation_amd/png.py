@@ -4,36 +4,15 @@ writer (reference main.py:102-103 ``cv2.imwrite(mask_%06
 ``PngEncoder(n, H, W)`` owns the device workspace and output buffers; ``encode(mask)`` enqueues the kernels on the
 current stream and returns device tensors ``(stream (n, stride) u8, lengths (n,) i32)`` holding each mask's zlib
 stream; ``png_file(H, W, stream_bytes)`` adds the PNG chunk framing on the host.  No CPU fallback."""
-import ctypes
 import struct
 import zlib
 
 import torch
 
 from . import _lib
-from ._runtime import current_stream_ptr
+from ._runtime import is_device_tensor, launch
 
-_FUNCS = None
 _SIGNATURE = b"\x89PNG\r\n\x1a\n"
-
-
-def _api():
-    global _FUNCS
-    if _FUNCS is None:
-        lib = _lib.load_library().lib
-        c = ctypes
-        vp, i32, i64 = c.c_void_p, c.c_int32, c.c_int64
-        sig = {
-            "gsa_png_workspace_bytes": (i64, [i32, i32, i32]),
-            "gsa_png_max_stream_bytes": (i64, [i32, i32]),
-            "gsa_png_encode": (c.c_int, [vp, i32, i32, i32, vp, vp, i64, vp, i64, vp]),
-        }
-        _FUNCS = {}
-        for name, (res, args) in sig.items():
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-            _FUNCS[name] = fn
-    return _FUNCS
 
 
 def _chunk(tag, data):
@@ -47,11 +26,11 @@ def png_file(H, W, idat):
 
 class PngEncoder:
     def __init__(self, n, H, W, device):
-        api = _api()
+        fn = _lib.load_library().fn
         self.n, self.H, self.W = n, H, W
         self.device = torch.device(device)
-        ws = api["gsa_png_workspace_bytes"](n, H, W)
-        worst = api["gsa_png_max_stream_bytes"](H, W)
+        ws = fn("gsa_png_workspace_bytes")(n, H, W)
+        worst = fn("gsa_png_max_stream_bytes")(H, W)
         if ws < 0 or worst < 0:
             raise ValueError("PNG encoder: the width must be a multiple of 16 px (got %dx%d); other sizes go through the "
                              "host encoder (DatasetWriter(gpu_png=False))" % (H, W))
@@ -62,16 +41,13 @@ class PngEncoder:
 
     def encode(self, mask):
         """mask: (k, H, W) uint8 CUDA tensor, k <= n.  -> (zlib streams (k, stride) u8, lengths (k,) i32), stream-ordered."""
-        if not mask.is_cuda or mask.dtype != torch.uint8 or not mask.is_contiguous():
+        if not is_device_tensor(mask, torch.uint8):
             raise ValueError("encode takes a contiguous uint8 CUDA tensor")
         k = mask.shape[0]
         if k > self.n or tuple(mask.shape[1:]) != (self.H, self.W):
             raise ValueError("mask batch %s does not fit the encoder (%d, %d, %d)" % (tuple(mask.shape), self.n, self.H, self.W))
-        with torch.cuda.device(mask.device):     # the C ABI is stateless: kernels go to the calling thread's current device
-            rc = _api()["gsa_png_encode"](current_stream_ptr(mask.device), k, self.H, self.W, mask.data_ptr(), self._ws.data_ptr(),
-                                          self._ws.numel(), self.out.data_ptr(), self.out_stride, self.lengths.data_ptr())
-        if rc != 0:
-            raise _lib.GsaError("gsa_png_encode failed (%d)" % rc)
+        launch("gsa_png_encode", mask.device, k, self.H, self.W, mask.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+               self.out.data_ptr(), self.out_stride, self.lengths.data_ptr())
         return self.out[:k], self.lengths[:k]
 
     def files(self, mask):

@@ -34,6 +34,19 @@ def splitmix64(x):
     return x ^ (x >> np.uint64(31))
 
 
+def uniform_draws(seed, seed_xor, first_index, n, k):
+    """float64 (n, k): per global sample ``i = first_index .. first_index+n-1`` the uniforms ``r_j = (u_j >> 11) * 2**-53`` in [0, 1)
+    of the chain ``u_0 = splitmix64((seed ^ seed_xor) ^ i)``, ``u_j = splitmix64(u_{j-1})`` -- the draws of the augmentation plans."""
+    idx = np.arange(n, dtype=np.uint64) + np.uint64(int(first_index) & _M64)
+    u = splitmix64(np.uint64((int(seed) & _M64) ^ seed_xor) ^ idx)
+    out = np.empty((n, k), np.float64)
+    for j in range(k):
+        if j:
+            u = splitmix64(u)
+        out[:, j] = (u >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    return out
+
+
 def mix_plan(seed, first_index, n, prob, num_layers):
     """(mix bool[n], cutoff int32[n]) of the global samples ``first_index .. first_index+n-1`` (module docstring)."""
     if num_layers < 2:

@@ -176,3 +176,37 @@ def sweep_setup(gan):
         z = np.concatenate([z, z2])
         noise = [np.concatenate([a, b]) for a, b in zip(noise, noise2)]
     return gcfg, gp, dcfg, dp, z, noise
+
+
+# ---- the C headers against the ctypes table (tests/test_abi_and_host.py; the per-module tests take their declared sets from here) ----
+_C_KINDS = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "uint32_t": "u32", "float": "float", "double": "double",
+            "void": "void"}
+
+
+def c_kind(text):
+    """The kind of a C type as written in a header: "pointer" for anything with a *, else one of _C_KINDS' values."""
+    return "pointer" if "*" in text else _C_KINDS[text.replace("const", "").strip()]
+
+
+def ctypes_kind(t):
+    """The kind of a ctypes result or argument type, in c_kind's terms."""
+    import ctypes as c
+    if t is None:
+        return "void"
+    if t in (c.c_void_p, c.c_char_p) or issubclass(t, c._Pointer):
+        return "pointer"
+    return {c.c_int: "i32", c.c_int32: "i32", c.c_int64: "i64", c.c_uint64: "u64", c.c_uint32: "u32", c.c_float: "float",
+            c.c_double: "double"}[t]
+
+
+def header_declarations(name):
+    """include/<name> -> (text without comments, {function: (result kind, [argument kinds])}) of every gsa_* function it declares."""
+    import os
+    import re
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", name)) as f:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    out = {}
+    for res, fn, args in re.findall(r"(?:^|[;{}])\s*((?:const\s+)?\w+[\s*]+)(gsa_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        args = [] if args.strip() == "void" else [re.sub(r"\w+\s*$", "", a) for a in args.split(",")]
+        out[fn] = (c_kind(res), [c_kind(a) for a in args])
+    return text, out

@@ -10,6 +10,7 @@ import pytest
 
 from gan_segmentation_amd import _lib
 from gan_segmentation_amd import dist as gdist
+from tests.common import ctypes_kind, header_declarations
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -21,30 +22,38 @@ def hip_library():
     return _lib.HIP_LIBRARY
 
 
+HEADERS = ("gsa.h", "gsa_train.h", "gsa_jpeg.h", "gsa_jpeg_roundtrip.h", "gsa_png.h", "gsa_augment.h", "gsa_mask.h",
+           "gsa_photometric.h", "gsa_stats.h")
+
+
+@pytest.mark.parametrize("header", HEADERS)
+def test_header_exports_and_table_agree(hip_library, header):
+    """include/<header> <-> the library's exports <-> the header's group of _lib.SIGNATURES: the same names, every one exported, and
+    bound with a result and arguments of the declared kinds, position by position (tests/common.py names the kinds)."""
+    declared = header_declarations(header)[1]
+    assert set(declared) == set(_lib.SIGNATURES[header])
+    lib, api = ctypes.CDLL(hip_library), _lib.Api(hip_library, "gsa_")
+    for name, kinds in declared.items():
+        assert hasattr(lib, name), "%s declared in %s but not exported" % (name, header)
+        fn = api.fn(name)
+        assert (ctypes_kind(fn.restype), [ctypes_kind(t) for t in fn.argtypes]) == kinds, name
+
+
 def test_header_symbols_are_exported(hip_library):
-    """Every function include/gsa.h declares is exported by the built library, and vice versa."""
-    with open(os.path.join(ROOT, "include", "gsa.h")) as f:
-        header = f.read()
-    declared = set(re.findall(r"\b(gsa_[a-z_]+)\s*\(", header)) - {"gsa_ctx"}
-    lib = ctypes.CDLL(hip_library)
-    for name in declared:
-        assert hasattr(lib, name), "%s declared in gsa.h but not exported" % name
-    assert declared == {"gsa_" + s for s in _lib.API_SYMBOLS}
+    """The table knows every header under include/ and every function of all of them once; what include/gsa.h declares is an
+    attribute of the Api without its prefix."""
+    assert sorted(os.listdir(os.path.join(ROOT, "include"))) == sorted(HEADERS) == sorted(_lib.SIGNATURES)
+    assert sum(len(header_declarations(h)[1]) for h in HEADERS) == len({n for g in _lib.SIGNATURES.values() for n in g}) == 55
     api = _lib.Api(hip_library, "gsa_")
+    for name in header_declarations("gsa.h")[1]:
+        assert getattr(api, name[len("gsa_"):]) is api.fn(name)
     assert b"gfx950" in api.version()
 
 
-def test_training_header_symbols_are_exported(hip_library):
-    """include/gsa_train.h (decoder-training operators) <-> library exports <-> the ctypes table of train_ops."""
-    with open(os.path.join(ROOT, "include", "gsa_train.h")) as f:
-        header = f.read()
-    declared = set(re.findall(r"\bint\s+(gsa_train_[a-z0-9_]+)\s*\(", header))
-    assert len(declared) == 13
-    lib = ctypes.CDLL(hip_library)
-    for name in declared:
-        assert hasattr(lib, name), "%s declared in gsa_train.h but not exported" % name
-    from gan_segmentation_amd import train_ops
-    assert set(train_ops._api().keys()) == declared
+def test_training_header_symbols_are_exported():
+    """include/gsa_train.h (decoder-training operators): thirteen entries, every one returning a status."""
+    declared = header_declarations("gsa_train.h")[1]
+    assert len(declared) == 13 and all(n.startswith("gsa_train_") and res == "i32" for n, (res, _args) in declared.items())
 
 
 def test_product_path_fails_loudly_without_gpu(hip_library):
@@ -102,6 +111,7 @@ sys.path.insert(0, %(root)r)
 import numpy as np, torch
 import torch.distributed as dist
 from gan_segmentation_amd import dist as gdist
+from tests.common import ctypes_kind, header_declarations
 from gan_segmentation_amd import weights as W
 from oracle.binding import Oracle
 rank, world, _ = gdist.init_from_env(backend="gloo")
@@ -302,6 +312,7 @@ sys.path.insert(0, ROOT_DIR)
 import numpy as np, torch
 import torch.distributed as dist
 from gan_segmentation_amd import dist as gdist
+from tests.common import ctypes_kind, header_declarations
 from gan_segmentation_amd import main as cli
 rank, world, _ = gdist.init_from_env(backend="gloo")
 assert world == 4
@@ -397,6 +408,7 @@ sys.path.insert(0, ROOT_DIR)
 import numpy as np, torch
 import torch.distributed as dist
 from gan_segmentation_amd import dist as gdist
+from tests.common import ctypes_kind, header_declarations
 import bench
 rank, world, _ = gdist.init_from_env(backend="gloo")
 assert world == 2

@@ -1,14 +1,9 @@
 """The training stream on the host side, without a GPU: the numpy restatement of the canonical rule of include/gsa_augment.h
 (``rule_augment``, which tests/test_gpu_augment.py holds the kernel to bit for bit), the augmentation plan and the stream's index
 arithmetic of gan-segmentation_amd/augment.py, the C ABI against the library's exports, and the keyword validation."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 
 
@@ -285,26 +280,19 @@ def test_endless_stream_and_bad_arguments():
 
 # -- the C ABI and the keyword validation --------------------------------------------------------------------------------------
 def test_augment_header_symbols_are_exported(hip_library):
-    """include/gsa_augment.h <-> the library's exports <-> the ctypes table of augment; bad arguments are GSA_ERR_INVALID before
-    any device work."""
-    with open(os.path.join(ROOT, "include", "gsa_augment.h")) as f:
-        text = f.read()
-    declared = set(re.findall(r"\bint\s+(gsa_augment_[a-z0-9_]+)\s*\(", text))
-    assert declared == {"gsa_augment_pairs"}
-    lib = ctypes.CDLL(hip_library)
-    for name in declared:
-        assert hasattr(lib, name), "%s declared in gsa_augment.h but not exported" % name
-    from gan_segmentation_amd import augment
-    api = augment._api()
-    assert set(api) == declared
+    """include/gsa_augment.h declares the one entry; bad arguments are GSA_ERR_INVALID before any device work."""
+    from gan_segmentation_amd._lib import load_library
+    from tests.common import header_declarations
+    assert set(header_declarations("gsa_augment.h")[1]) == {"gsa_augment_pairs"}
+    fn = load_library().fn("gsa_augment_pairs")
     buf = np.zeros(64, np.float32)          # stands in for every pointer: no argument set below gets as far as a launch
     p = buf.ctypes.data
     good = dict(n=1, H=8, W=8, C=3, img=p, mask=p, m=p, scale=p, bias=p, oh=8, ow=8, bf=0, ignore=255, out=p, label=p)
 
     def call(**kw):
         a = dict(good, **kw)
-        return api["gsa_augment_pairs"](None, a["n"], a["H"], a["W"], a["C"], a["img"], a["mask"], a["m"], a["scale"], a["bias"],
-                                        a["oh"], a["ow"], a["bf"], a["ignore"], a["out"], a["label"])
+        return fn(None, a["n"], a["H"], a["W"], a["C"], a["img"], a["mask"], a["m"], a["scale"], a["bias"], a["oh"], a["ow"], a["bf"],
+                  a["ignore"], a["out"], a["label"])
     for bad in (dict(C=5), dict(C=0), dict(n=-1), dict(H=0), dict(W=0), dict(W=(1 << 24) + 1), dict(oh=6), dict(ow=0), dict(ow=10),
                 dict(bf=2), dict(ignore=256), dict(ignore=-1), dict(img=None), dict(mask=None), dict(m=None), dict(scale=None),
                 dict(bias=None), dict(out=None), dict(label=None), dict(out=p + 4), dict(label=p + 1), dict(bf=1, out=p + 4),

@@ -5,7 +5,6 @@
 import ctypes
 import io
 import os
-import re
 
 import numpy as np
 import pytest
@@ -83,19 +82,15 @@ def test_header_of_the_product_library(hip_library):
 
 
 def test_jpeg_header_symbols_are_exported(hip_library):
-    with open(os.path.join(ROOT, "include", "gsa_jpeg.h")) as f:
-        text = f.read()
-    declared = set(re.findall(r"\b(gsa_jpeg_[a-z0-9_]+)\s*\(", text))
+    from gan_segmentation_amd._lib import load_library
+    from tests.common import header_declarations
+    declared = set(header_declarations("gsa_jpeg.h")[1])
     assert declared == {"gsa_jpeg_header", "gsa_jpeg_workspace_bytes", "gsa_jpeg_max_scan_bytes", "gsa_jpeg_encode"}
-    lib = ctypes.CDLL(hip_library)
-    for name in declared:
-        assert hasattr(lib, name), "%s declared in gsa_jpeg.h but not exported" % name
-    from gan_segmentation_amd import jpeg
-    assert set(jpeg._api().keys()) == declared
+    fn = load_library().fn
     # argument checks that need no GPU
-    assert jpeg._api()["gsa_jpeg_workspace_bytes"](1, 100, 64, 4) < 0          # not a multiple of 16
-    assert jpeg._api()["gsa_jpeg_workspace_bytes"](1, 64, 64, 0) < 0           # restart interval required
-    assert jpeg._api()["gsa_jpeg_max_scan_bytes"](1024, 1024, 4) == 4096 * 6 * 448 + 1024 * 3 + 2
+    assert fn("gsa_jpeg_workspace_bytes")(1, 100, 64, 4) < 0          # not a multiple of 16
+    assert fn("gsa_jpeg_workspace_bytes")(1, 64, 64, 0) < 0           # restart interval required
+    assert fn("gsa_jpeg_max_scan_bytes")(1024, 1024, 4) == 4096 * 6 * 448 + 1024 * 3 + 2
 
 
 @pytest.mark.gpu
@@ -165,9 +160,9 @@ def test_dataset_writer_with_gpu_jpeg(torch_cuda, tmp_path):
 def test_encode_rejects_bad_arguments_before_touching_the_gpu(hip_library):
     """Argument validation of gsa_jpeg_encode happens on the host (no HIP call precedes it): sizes that are not
     multiples of 16, a missing restart interval, null / misaligned pointers, a workspace that is too small."""
-    from gan_segmentation_amd import jpeg
-    enc = jpeg._api()["gsa_jpeg_encode"]
-    ws = jpeg._api()["gsa_jpeg_workspace_bytes"](1, 64, 64, 2)
+    from gan_segmentation_amd._lib import load_library
+    enc = load_library().fn("gsa_jpeg_encode")
+    ws = load_library().fn("gsa_jpeg_workspace_bytes")(1, 64, 64, 2)
     good = dict(n=1, H=64, W=64, rgb=4096, q=95, ri=2, ws=8192, wsb=ws, out=16384, stride=1 << 20, ln=32768)
 
     def call(**kw):

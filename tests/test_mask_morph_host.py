@@ -9,9 +9,7 @@ every stage.  It is PINNED here, with zero differing bytes allowed, against
 * a committed fixture (tests/golden/mask_morph.npz), which holds without scipy or Pillow.
 The GPU tests (tests/test_gpu_mask_morph.py) hold the kernel to this rule bit for bit.  Also here: hand cases, a guard that the
 inputs can tell the rule from a zero-padded erosion, the C ABI's symbols and the validation of the keyword and the key."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -242,24 +240,17 @@ def test_the_inputs_can_tell_the_rule_from_a_zero_padded_erosion():
 
 
 # -- the C ABI -----------------------------------------------------------------------------------------------------------------
-def test_mask_header_symbols_are_exported(hip_library):
-    """include/gsa_mask.h <-> library exports <-> the ctypes table of mask_ops."""
-    with open(os.path.join(ROOT, "include", "gsa_mask.h")) as f:
-        header = f.read()
-    declared = set(re.findall(r"\bint\s+(gsa_mask_[a-z0-9_]+)\s*\(", header))
-    assert declared == {"gsa_mask_morph"}
-    lib = ctypes.CDLL(hip_library)
-    for name in declared:
-        assert hasattr(lib, name), "%s declared in gsa_mask.h but not exported" % name
-    from gan_segmentation_amd import mask_ops
-    assert set(mask_ops._api().keys()) == declared
+def test_mask_header_symbols_are_exported():
+    """include/gsa_mask.h declares the one entry (tests/test_abi_and_host.py checks its export and its ctypes row)."""
+    from tests.common import header_declarations
+    assert set(header_declarations("gsa_mask.h")[1]) == {"gsa_mask_morph"}
 
 
 def test_morph_rejects_bad_arguments_before_touching_the_gpu(hip_library):
     """Argument validation of gsa_mask_morph happens on the host (no HIP call precedes it): a negative batch, sizes outside 1..65535,
     null or overlapping pointers; an empty batch is a successful no-op."""
-    from gan_segmentation_amd import mask_ops
-    fn = mask_ops._api()["gsa_mask_morph"]
+    from gan_segmentation_amd._lib import load_library
+    fn = load_library().fn("gsa_mask_morph")
     good = dict(n=2, H=32, W=48, mask=1 << 20, out=2 << 20)
 
     def call(**kw):

@@ -4,7 +4,6 @@ key; DatasetWriter(stats=...)).
 ``rule_stats(img, mask)`` is the canonical rule in numpy, written the slow obvious way: a boolean mask per slot, np.nonzero for the
 boxes, int64 sums.  It is held here against rows computed by hand and against invariants; the GPU tests
 (tests/test_gpu_pair_stats.py) hold the kernel to it bit for bit."""
-import ctypes
 import json
 import os
 import re
@@ -247,22 +246,16 @@ def test_merge_refuses_duplicates_gaps_and_mixed_sizes(tmp_path, capsys):
 
 # -- the C ABI -------------------------------------------------------------------------------------------------------------------
 def test_header_symbols_are_exported(hip_library):
-    """include/gsa_stats.h <-> library exports <-> the ctypes table of pair_stats; include/gsa.h does not know the entry."""
-    header = open(os.path.join(ROOT, "include", "gsa_stats.h")).read()
-    declared = set(re.findall(r"\bint\s+(gsa_[a-z0-9_]+)\s*\(", header))
-    assert declared == {"gsa_pair_stats"}
-    lib = ctypes.CDLL(hip_library)
-    for name in declared:
-        assert hasattr(lib, name), "%s declared in gsa_stats.h but not exported" % name
-    from gan_segmentation_amd import pair_stats
-    assert set(pair_stats._api().keys()) == declared
+    """include/gsa_stats.h declares the one entry; include/gsa.h does not know it."""
+    from tests.common import header_declarations
+    assert set(header_declarations("gsa_stats.h")[1]) == {"gsa_pair_stats"}
     assert "gsa_pair_stats" not in open(os.path.join(ROOT, "include", "gsa.h")).read()
 
 
 def test_entry_rejects_bad_arguments_before_touching_the_gpu(hip_library):
     """Argument validation happens on the host (no HIP call precedes it); an empty batch is a successful no-op."""
-    from gan_segmentation_amd import pair_stats
-    fn = pair_stats._api()["gsa_pair_stats"]
+    from gan_segmentation_amd._lib import load_library
+    fn = load_library().fn("gsa_pair_stats")
     good = dict(n=2, H=32, W=48, C=3, img=1 << 20, mask=2 << 20, rows=3 << 20)
 
     def call(**kw):

@@ -5,18 +5,12 @@ ImageGenerator.training_batches(photometric=...)).
 7-tap blur with a reflect-101 border accumulated in tap order, ``c = b*alpha + offset[ch]``, ``v = c + noise_sigma*g`` with ``g`` from
 the byte sum of one Philox4x32-10 block per value (oracle/ref_philox.py), ``uint8(floor(clamp(v, 0, 255) + 0.5))``.  The GPU tests
 (tests/test_gpu_photometric.py) hold the kernel to it byte for byte.  Also here: identity and constant images, the plan (the
-splitmix chain, batch independence, the weights, the gates, the limits' checks), the noise source's moments, the header against
-the library's exports and the ctypes table, and the C entry's argument checks with a null stream."""
-import ctypes
-import os
-import re
-
+splitmix chain, batch independence, the weights, the gates, the limits' checks), the noise source's moments, the header's entry
+and row length, and the C entry's argument checks with a null stream."""
 import numpy as np
 import pytest
 
 from oracle.ref_philox import philox4x32_10
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 INV_STD = np.float32(1.0 / 295.6010825419961)
 COUNTER_TAG = 0x50480000
@@ -278,26 +272,20 @@ def test_noise_blocks_differ_by_pixel_channel_index_and_seed():
 
 # -- the C ABI -----------------------------------------------------------------------------------------------------------------
 def test_photometric_header_symbols_are_exported(hip_library):
-    """include/gsa_photometric.h <-> library exports <-> the ctypes table of photometric."""
-    with open(os.path.join(ROOT, "include", "gsa_photometric.h")) as f:
-        header = f.read()
-    declared = set(re.findall(r"\bint\s+(gsa_photometric[a-z0-9_]*)\s*\(", header))
-    assert declared == {"gsa_photometric"}
-    lib = ctypes.CDLL(hip_library)
-    for name in declared:
-        assert hasattr(lib, name), "%s declared in gsa_photometric.h but not exported" % name
-    from gan_segmentation_amd import photometric as ph
-    assert set(ph._api().keys()) == declared
+    """include/gsa_photometric.h declares the one entry, of ten arguments, and the row length of photometric."""
+    from gan_segmentation_amd import _lib, photometric as ph
+    from tests.common import header_declarations
+    header, declared = header_declarations("gsa_photometric.h")
+    assert set(declared) == {"gsa_photometric"}
     assert "#define GSA_PHOTOMETRIC_ROW %d" % ph.ROW in header
-    proto = re.search(r"int gsa_photometric\(([^)]*)\)", header).group(1)
-    assert len(proto.split(",")) == len(ph._api()["gsa_photometric"].argtypes) == 10
+    assert len(declared["gsa_photometric"][1]) == len(_lib.load_library().fn("gsa_photometric").argtypes) == 10
 
 
 def test_photometric_rejects_bad_arguments_before_touching_the_gpu(hip_library):
     """Argument validation of gsa_photometric happens on the host (no HIP call precedes it, the stream is null): channels outside
     1..4, H or W below 4, more than 2^31 pixels, null pointers, out == img; an empty batch is a successful no-op."""
-    from gan_segmentation_amd import photometric as ph
-    fn = ph._api()["gsa_photometric"]
+    from gan_segmentation_amd._lib import load_library
+    fn = load_library().fn("gsa_photometric")
     good = dict(n=2, H=32, W=48, C=3, img=1 << 20, params=4 << 20, out=2 << 20)
 
     def call(**kw):

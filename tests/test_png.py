@@ -2,16 +2,12 @@
 * CPU: the Python restatement (oracle/ref_png.py) is pinned by zlib itself -- inflating its stream gives the filtered
   scanlines, a PNG reader gives the mask back; the C ABI of include/gsa_png.h against the library exports;
 * GPU (-m gpu): csrc/gsa_png.hip byte for byte against the restatement on small masks, decoded back on full sizes."""
-import ctypes
 import io
 import os
-import re
 import zlib
 
 import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def masks(rng, H, W):
@@ -43,24 +39,18 @@ def test_restatement_is_a_valid_zlib_stream(H, W):
 
 
 def test_png_header_symbols_are_exported(hip_library):
-    with open(os.path.join(ROOT, "include", "gsa_png.h")) as f:
-        text = f.read()
-    declared = set(re.findall(r"\b(gsa_png_[a-z0-9_]+)\s*\(", text))
-    assert declared == {"gsa_png_workspace_bytes", "gsa_png_max_stream_bytes", "gsa_png_encode"}
-    lib = ctypes.CDLL(hip_library)
-    for name in declared:
-        assert hasattr(lib, name), "%s declared in gsa_png.h but not exported" % name
-    from gan_segmentation_amd import png
-    api = png._api()
-    assert set(api.keys()) == declared
-    assert api["gsa_png_workspace_bytes"](1, 64, 60) < 0 and api["gsa_png_max_stream_bytes"](64, 8) < 0     # W % 16
-    ws = api["gsa_png_workspace_bytes"](2, 64, 64)
+    from gan_segmentation_amd._lib import load_library
+    from tests.common import header_declarations
+    assert set(header_declarations("gsa_png.h")[1]) == {"gsa_png_workspace_bytes", "gsa_png_max_stream_bytes", "gsa_png_encode"}
+    fn = load_library().fn
+    assert fn("gsa_png_workspace_bytes")(1, 64, 60) < 0 and fn("gsa_png_max_stream_bytes")(64, 8) < 0     # W % 16
+    ws = fn("gsa_png_workspace_bytes")(2, 64, 64)
     assert ws > 0
     good = dict(n=2, H=64, W=64, mask=4096, ws=8192, wsb=ws, out=1 << 20, stride=1 << 16, ln=1 << 22)
 
     def call(**kw):          # argument validation happens on the host, before any HIP call
         a = dict(good, **kw)
-        return api["gsa_png_encode"](None, a["n"], a["H"], a["W"], a["mask"], a["ws"], a["wsb"], a["out"], a["stride"], a["ln"])
+        return fn("gsa_png_encode")(None, a["n"], a["H"], a["W"], a["mask"], a["ws"], a["wsb"], a["out"], a["stride"], a["ln"])
 
     for bad in (dict(n=0), dict(W=40), dict(H=0), dict(mask=None), dict(mask=4100), dict(ws=None), dict(wsb=ws - 1), dict(out=None),
                 dict(ln=None), dict(stride=4)):
