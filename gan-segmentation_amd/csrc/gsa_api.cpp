@@ -20,6 +20,7 @@
 
 #include "../../include/gsa.h"
 #include "gsa_kernels.h"
+#include "gsa_pack.h"
 
 using namespace gsa;
 
@@ -168,38 +169,27 @@ int nf(const gsa_generator_config& g, int r) {
     return fmaps < g.fmap_max ? fmaps : g.fmap_max;
 }
 
-// (W*std)*lr_mult -- two fp32 roundings, reference networks_stylegan.py:407-412,513-518
-inline float eff(float w, float std, bool use_std, float lr) {
-    float v = use_std ? w * std : w;
-    return v * lr;
-}
-
-int upload(gsa_ctx* c, const std::vector<float>& h, float** out, std::vector<void*>& track) {
+template <typename E>
+int upload(gsa_ctx* c, const E* h, size_t count, E** out, std::vector<void*>& track) {
     void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, h.size() * sizeof(float) + 16));
+    HIP_TRY(hipMalloc(&d, count * sizeof(E) + 16));
     track.push_back(d);
-    HIP_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    *out = (float*)d;
+    HIP_TRY(hipMemcpy(d, h, count * sizeof(E), hipMemcpyHostToDevice));
+    *out = (E*)d;
     return GSA_OK;
 }
 
-// round-to-nearest-even fp32 -> bf16 (what v_cvt_pk_bf16_f32 does to the activations)
-inline uint16_t bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
+template <typename E>
+int upload(gsa_ctx* c, const std::vector<E>& h, E** out, std::vector<void*>& track) {
+    return upload(c, h.data(), h.size(), out, track);
 }
 
-// Upload of an MFMA weight pack (a sequence of 256-float [ci][16][cg] chunks, one per tap and
-// (16 couts, 16 channels) pair).  bf16 mode: each chunk becomes [kq][16][4] bf16 with channel = 4*kq+j,
-// the k order of v_mfma_f32_16x16x16_bf16 -- half the bytes, addressed in the same 4-byte slots.
+// Upload of an MFMA weight pack (a sequence of 256-float [ci][16][cg] chunks, one per tap and (16 couts, 16 channels) pair):
+// as it is, or in bf16 mode repacked to bf16 (gsa_pack_bf16)
 int upload_mfma(gsa_ctx* c, const std::vector<float>& h, float** out, std::vector<void*>& track) {
     if (!c->bf16) return upload(c, h, out, track);
     std::vector<float> packed(h.size() / 2);
-    uint16_t* o = reinterpret_cast<uint16_t*>(packed.data());
-    for (size_t i = 0; i < h.size(); ++i) o[i] = bf16_rne(h[i]);      // [kq][16][j], channel 4kq+j: the fp32 pack order already
+    gsa_pack_bf16(h.data(), h.size(), reinterpret_cast<uint16_t*>(packed.data()));
     return upload(c, packed, out, track);
 }
 
@@ -212,183 +202,22 @@ int dev_alloc(gsa_ctx* c, size_t count, T** out, std::vector<void*>& track) {
     return GSA_OK;
 }
 
+template <typename T>
+int dev_alloc_zeroed(gsa_ctx* c, size_t count, T** out, std::vector<void*>& track) {
+    if (int rc = dev_alloc(c, count, out, track)) return rc;
+    HIP_TRY(hipMemset(*out, 0, count * sizeof(T)));
+    return GSA_OK;
+}
+
 void free_all(std::vector<void*>& v) {
     for (void* p : v) (void)hipFree(p);
     v.clear();
 }
 
-// conv OIHW (O,I,3,3) -> [O/16][I/16][tap][ci][16][cg]; channel = 16cb+4ci+cg (ci = k slot of the MFMA, cg = which of the
-// four MFMAs of the (tap, block)), cout = 16g+n
-std::vector<float> pack_conv3(const float* w, int O, int I, float std, bool us, float lr) {
-    const int ct = 16;
-    std::vector<float> out((size_t)O * I * 9);
-    const int nblk = I / 16, G = O / ct;
-    for (int g = 0; g < G; ++g)
-        for (int cb = 0; cb < nblk; ++cb)
-            for (int t = 0; t < 9; ++t)
-                for (int ci = 0; ci < 4; ++ci)
-                    for (int n = 0; n < ct; ++n)
-                        for (int cg = 0; cg < 4; ++cg) {
-                            const int o = g * ct + n, ch = cb * 16 + ci * 4 + cg;
-                            out[((((((size_t)g * nblk + cb) * 9 + t) * 4 + ci) * ct + n) * 4) + cg] =
-                                eff(w[((size_t)o * I + ch) * 9 + t], std, us, lr);
-                        }
-    return out;
-}
-
-// deconv IOHW (I,O,4,4) -> [O/16][I/16][tap16][ci][16][cg]
-std::vector<float> pack_deconv(const float* w, int I, int O, float std, bool us, float lr) {
-    const int ct = 16;
-    std::vector<float> out((size_t)O * I * 16);
-    const int nblk = I / 16, G = O / ct;
-    for (int g = 0; g < G; ++g)
-        for (int cb = 0; cb < nblk; ++cb)
-            for (int t = 0; t < 16; ++t)
-                for (int ci = 0; ci < 4; ++ci)
-                    for (int n = 0; n < ct; ++n)
-                        for (int cg = 0; cg < 4; ++cg) {
-                            const int o = g * ct + n, ch = cb * 16 + ci * 4 + cg;
-                            out[((((((size_t)g * nblk + cb) * 16 + t) * 4 + ci) * ct + n) * 4) + cg] =
-                                eff(w[((size_t)ch * O + o) * 16 + t], std, us, lr);
-                        }
-    return out;
-}
-
-// nearest-x2 + conv3x3 (OIHW (O,I,3,3)) in sub-pixel form: the equivalent stride-2 transposed
-// 4x4 kernel Wd[a][b] = sum_{ky in S(a)} sum_{kx in S(b)} W[ky][kx], S(0)={2} S(1)={1,2}
-// S(2)={0,1} S(3)={0}; fp32 sums, ky then kx ascending, left to right (canonical order,
-// DESIGN.md).  Packed like a deconv: [O/16][I/16][tap16][ci][16][cg].
-std::vector<float> pack_upconv(const float* w, int O, int I, float std, bool us, float lr) {
-    static const int S[4][2] = {{2, -1}, {1, 2}, {0, 1}, {0, -1}};
-    std::vector<float> out((size_t)O * I * 16);
-    const int nblk = I / 16, G = O / 16;
-    for (int g = 0; g < G; ++g)
-        for (int cb = 0; cb < nblk; ++cb)
-            for (int a = 0; a < 4; ++a)
-                for (int b = 0; b < 4; ++b)
-                    for (int ci = 0; ci < 4; ++ci)
-                        for (int n = 0; n < 16; ++n)
-                            for (int cg = 0; cg < 4; ++cg) {
-                                const int o = g * 16 + n, ch = cb * 16 + ci * 4 + cg;
-                                const float* wk = w + ((size_t)o * I + ch) * 9;
-                                float sum = 0.0f;
-                                bool first = true;
-                                for (int i = 0; i < 2; ++i)
-                                    for (int j = 0; j < 2; ++j) {
-                                        if (S[a][i] < 0 || S[b][j] < 0) continue;
-                                        const float e = eff(wk[S[a][i] * 3 + S[b][j]], std, us, lr);
-                                        sum = first ? e : sum + e;
-                                        first = false;
-                                    }
-                                out[((((((size_t)g * nblk + cb) * 16 + a * 4 + b) * 4 + ci) * 16 + n) * 4) + cg] = sum;
-                            }
-    return out;
-}
-
-// 1x1 shortcut (O,I,1,1) -> [O/16][I/16][ci][16][cg]
-std::vector<float> pack_conv1(const float* w, int O, int I) {
-    const int ct = 16;
-    std::vector<float> out((size_t)O * I);
-    const int nblk = I / 16, G = O / ct;
-    for (int g = 0; g < G; ++g)
-        for (int cb = 0; cb < nblk; ++cb)
-            for (int ci = 0; ci < 4; ++ci)
-                for (int n = 0; n < ct; ++n)
-                    for (int cg = 0; cg < 4; ++cg)
-                        out[(((((size_t)g * nblk + cb) * 4 + ci) * ct + n) * 4) + cg] =
-                            w[(size_t)(g * ct + n) * I + cb * 16 + ci * 4 + cg];
-    return out;
-}
-
-// Winograd F(2x2,3x3) weights of a 3x3 conv OIHW (O,I,3,3): U = G g G^T evaluated in double on the effective fp32
-// weights and rounded once (canonical arithmetic; the oracle's pack_wino is the same code path restated),
-// packed like a 16-tap kernel: [O/16][I/16][f = 4i+j][ci][16][cg]
-std::vector<float> pack_wino(const float* w, int O, int I, float std, bool us, float lr) {
-    std::vector<float> out((size_t)O * I * 16);
-    const int nblk = I / 16, G = O / 16;
-    for (int g = 0; g < G; ++g)
-        for (int cb = 0; cb < nblk; ++cb)
-            for (int ci = 0; ci < 4; ++ci)
-                for (int n = 0; n < 16; ++n)
-                    for (int cg = 0; cg < 4; ++cg) {
-                        const int o = g * 16 + n, ch = cb * 16 + ci * 4 + cg;
-                        const float* wk = w + ((size_t)o * I + ch) * 9;
-                        double k[3][3], r[4][3], u[4][4];
-                        for (int a = 0; a < 3; ++a)
-                            for (int b = 0; b < 3; ++b) k[a][b] = (double)eff(wk[a * 3 + b], std, us, lr);
-                        for (int b = 0; b < 3; ++b) {
-                            r[0][b] = k[0][b];
-                            r[1][b] = 0.5 * ((k[0][b] + k[1][b]) + k[2][b]);
-                            r[2][b] = 0.5 * ((k[0][b] - k[1][b]) + k[2][b]);
-                            r[3][b] = k[2][b];
-                        }
-                        for (int a = 0; a < 4; ++a) {
-                            u[a][0] = r[a][0];
-                            u[a][1] = 0.5 * ((r[a][0] + r[a][1]) + r[a][2]);
-                            u[a][2] = 0.5 * ((r[a][0] - r[a][1]) + r[a][2]);
-                            u[a][3] = r[a][2];
-                        }
-                        for (int f = 0; f < 16; ++f)
-                            out[((((((size_t)g * nblk + cb) * 16 + f) * 4 + ci) * 16 + n) * 4) + cg] = (float)u[f >> 2][f & 3];
-                    }
-    return out;
-}
-
-// Winograd F(4x4,3x3) weights (round 4): U = G g G^T with Lavin & Gray's 6x3 G, evaluated in double on the effective fp32 weights
-// and rounded once (the oracle's pack_wino43 restated), packed per 8-CHANNEL block [O/16][I/8][f = 6i+j][kq][16][j2] with
-// channel = 8b + 2kq + j2 (the K order of these layers: conv3x3_wino43): a lane's weight pair is one 8-byte LDS read
-std::vector<float> pack_wino43(const float* w, int O, int I, float std, bool us, float lr) {
-    static const double G[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
-    std::vector<float> out((size_t)O * I * 36);
-    const int nblk = I / 8, NG = O / 16;
-    for (int g = 0; g < NG; ++g)
-        for (int cb = 0; cb < nblk; ++cb)
-            for (int kq = 0; kq < 4; ++kq)
-                for (int n = 0; n < 16; ++n)
-                    for (int j2 = 0; j2 < 2; ++j2) {
-                        const int o = g * 16 + n, ch = cb * 8 + kq * 2 + j2;
-                        const float* wk = w + ((size_t)o * I + ch) * 9;
-                        double k[3][3], r[6][3];
-                        for (int a = 0; a < 3; ++a)
-                            for (int b = 0; b < 3; ++b) k[a][b] = (double)eff(wk[a * 3 + b], std, us, lr);
-                        for (int i = 0; i < 6; ++i)
-                            for (int b = 0; b < 3; ++b) r[i][b] = (G[i][0] * k[0][b] + G[i][1] * k[1][b]) + G[i][2] * k[2][b];
-                        for (int i = 0; i < 6; ++i)
-                            for (int j = 0; j < 6; ++j)
-                                out[((((((size_t)g * nblk + cb) * 36 + i * 6 + j) * 4 + kq) * 16 + n) * 2) + j2] =
-                                    (float)((r[i][0] * G[j][0] + r[i][1] * G[j][1]) + r[i][2] * G[j][2]);
-                    }
-    return out;
-}
-// static rule of the F(4x4,3x3) form (gsa_kernels.hip conv_uses_wino43): a Winograd layer with >= 64 input channels and >= 32 px
-inline bool wino43_layer(const gsa_ctx* c, int R, int Cin, int Cout);
-
-// the static rule of the Winograd form (gsa_kernels.hip conv_uses_wino): plain 3x3 convs with outputs >= 64 px, or >= 32 px with
-// at least 64 output channels (fewer tiles than that leave the chip idle: the direct small-tile kernels are faster there), fp32 mode
-inline bool wino_layer(const gsa_ctx* c, int R, int Cout) { return !c->bf16 && (R >= 64 || (R >= 32 && Cout >= 64) || (R >= 16 && Cout >= 256)); }
-inline bool wino43_layer(const gsa_ctx* c, int R, int Cin, int Cout) { return wino43_enabled() && wino_layer(c, R, Cout) && Cin >= 64 && R >= 32; }
-
-// final conv (K,I,3,3) -> [cb][tap][c16][K]
-std::vector<float> pack_final(const float* w, int K, int I) {
-    std::vector<float> out((size_t)K * I * 9);
-    for (int cb = 0; cb < I / 16; ++cb)
-        for (int t = 0; t < 9; ++t)
-            for (int ci = 0; ci < 16; ++ci)
-                for (int o = 0; o < K; ++o)
-                    out[(((size_t)cb * 9 + t) * 16 + ci) * K + o] = w[((size_t)o * I + cb * 16 + ci) * 9 + t];
-    return out;
-}
-
-const HostTensor* find(const std::map<std::string, HostTensor>& m, const std::string& name) {
-    auto it = m.find(name);
-    return it == m.end() ? nullptr : &it->second;
-}
-
-int need(gsa_ctx* c, const std::map<std::string, HostTensor>& m, const std::string& name, size_t count,
-         const float** out) {
-    const HostTensor* t = find(m, name);
-    if (!t) return fail(c, GSA_ERR_MISSING_PARAM, "parameter %s was not set", name.c_str());
+int need(gsa_ctx* c, const std::map<std::string, HostTensor>& m, const std::string& name, size_t count, const float** out) {
+    const auto it = m.find(name);
+    if (it == m.end()) return fail(c, GSA_ERR_MISSING_PARAM, "parameter %s was not set", name.c_str());
+    const HostTensor* t = &it->second;
     if (t->data.size() != count)
         return fail(c, GSA_ERR_INVALID, "parameter %s has %zu elements, expected %zu", name.c_str(), t->data.size(), count);
     *out = t->data.data();
@@ -396,6 +225,31 @@ int need(gsa_ctx* c, const std::map<std::string, HostTensor>& m, const std::stri
 }
 
 #define NEED(map, name, count, ptr) do { int rc_ = need(c, map, name, count, ptr); if (rc_) return rc_; } while (0)
+
+// a parameter that goes to the device as it was set
+int upload_param(gsa_ctx* c, const std::map<std::string, HostTensor>& m, const std::string& name, size_t count, float** out, std::vector<void*>& track) {
+    const float* p;
+    NEED(m, name, count, &p);
+    return upload(c, p, count, out, track);
+}
+
+// A blocked MFMA pack (gsa_pack.h) of the weight (a, b, taps): packed on the host, uploaded in the precision's operand format
+using PackFn = void (*)(const float*, int, int, float, int, float, float*);
+int upload_pack(gsa_ctx* c, PackFn pack, const float* w, int a, int b, int taps, float std, bool us, float** out, std::vector<void*>& track) {
+    std::vector<float> h((size_t)a * b * taps);
+    pack(w, a, b, std, us, 1.0f, h.data());
+    return upload_mfma(c, h, out, track);
+}
+
+// The Winograd panel U of a 3x3 conv (O,I,3,3) with R px outputs where wino_shape (gsa_kernels.h) selects the form, whatever GSA_WINO
+// says; *out is untouched otherwise.  f43_ok: no residual epilogue, so the experiments build may give it the F(4x4,3x3) form.
+int upload_wino(gsa_ctx* c, const float* w, int O, int I, int R, bool f43_ok, float std, bool us, float** out, std::vector<void*>& track) {
+    if (!wino_shape(R, O, c->bf16)) return GSA_OK;
+    const bool f43 = f43_ok && wino43_enabled() && wino43_shape(R, I);
+    std::vector<float> h((size_t)O * I * (f43 ? 36 : 16));
+    (f43 ? gsa_pack_wino43 : gsa_pack_wino)(w, O, I, std, us, 1.0f, h.data());
+    return upload(c, h, out, track);
+}
 
 int get_std(gsa_ctx* c, const std::string& prefix, float* std) {
     *std = 1.0f;
@@ -444,10 +298,6 @@ int set_param(gsa_ctx* c, std::map<std::string, HostTensor>& m, const char* name
     t.data.assign(data, data + cnt);
     m[name] = std::move(t);
     return GSA_OK;
-}
-
-void reset_generator_dev(gsa_ctx* c) {
-    c->g_ready = false;
 }
 
 // ---------------------------------------------------------------- profiling wrapper
@@ -628,7 +478,7 @@ int gsa_generator_init(gsa_ctx* c, const gsa_generator_config* g) {
     }
     c->gparams.clear();
     c->g_init = true;
-    reset_generator_dev(c);
+    c->g_ready = false;
     return GSA_OK;
 }
 
@@ -657,25 +507,17 @@ int gsa_generator_commit(gsa_ctx* c) {
 
     const int C0 = c->ch[0];
     NEED(P, "constant_tensor", (size_t)C0 * 16, &w);
-    h.assign((size_t)C0 * 16, 0.f);
-    for (int ch = 0; ch < C0; ++ch)
-        for (int p = 0; p < 16; ++p) h[(size_t)p * C0 + ch] = w[ch * 16 + p];
+    h.resize((size_t)C0 * 16); gsa_pack_constant(w, C0, h.data());
     if (int rc = upload(c, h, &c->constant, T)) return rc;
-    NEED(P, "latent_avg", 512, &w);
-    h.assign(w, w + 512);
-    if (int rc = upload(c, h, &c->latent_avg, T)) return rc;
-    NEED(P, "truncation_psi", (size_t)2 * c->nlev, &w);
-    h.assign(w, w + 2 * c->nlev);
-    if (int rc = upload(c, h, &c->psi, T)) return rc;
+    if (int rc = upload_param(c, P, "latent_avg", 512, &c->latent_avg, T)) return rc;
+    if (int rc = upload_param(c, P, "truncation_psi", (size_t)2 * c->nlev, &c->psi, T)) return rc;
 
     for (int i = 0; i < 8; ++i) {
         snprintf(nm, sizeof nm, "mp_dense_%d", i);
         if (int rc = get_std(c, nm, &std)) return rc;
         NEED(P, std::string(nm) + "_weight", (size_t)L * L, &w);
         NEED(P, std::string(nm) + "_bias", (size_t)L, &b);
-        h.assign((size_t)L * L, 0.f);
-        for (int j = 0; j < L; ++j)
-            for (int k = 0; k < L; ++k) h[(size_t)k * L + j] = eff(w[(size_t)j * L + k], std, us, 0.01f);  // lr_mult 0.01, reference :135
+        h.resize((size_t)L * L); gsa_pack_mapping(w, L, std, us, h.data());
         if (int rc = upload(c, h, &c->map_wt[i], T)) return rc;
         h.assign((size_t)L, 0.f);
         for (int j = 0; j < L; ++j) h[j] = b[j] * 0.01f;
@@ -697,49 +539,35 @@ int gsa_generator_commit(gsa_ctx* c) {
         if (B.has_conv1) {
             snprintf(nm, sizeof nm, "%d_%s", R, B.is_deconv ? "deconv_1" : "conv_1");
             if (int rc = get_std(c, nm, &std)) return rc;
-            if (B.is_deconv) {
-                NEED(P, std::string(nm) + "_weight", (size_t)Cin * C * 16, &w);
-                h = pack_deconv(w, Cin, C, std, us, 1.0f);
-            } else {
-                NEED(P, std::string(nm) + "_weight", (size_t)Cin * C * 9, &w);
-                h = R >= 16 ? pack_upconv(w, C, Cin, std, us, 1.0f) : pack_conv3(w, C, Cin, std, us, 1.0f);
-            }
-            if (int rc = upload_mfma(c, h, &B.w1, T)) return rc;
+            NEED(P, std::string(nm) + "_weight", (size_t)Cin * C * (B.is_deconv ? 16 : 9), &w);
+            if (int rc = B.is_deconv ? upload_pack(c, gsa_pack_deconv, w, Cin, C, 16, std, us, &B.w1, T)
+                       : R >= 16     ? upload_pack(c, gsa_pack_upconv, w, C, Cin, 16, std, us, &B.w1, T)
+                                     : upload_pack(c, gsa_pack_conv3, w, C, Cin, 9, std, us, &B.w1, T)) return rc;
             snprintf(nm, sizeof nm, "%d_blur_1_w_kernel", R);
-            NEED(P, nm, (size_t)C * 9, &w);
-            h.assign(w, w + (size_t)C * 9);
-            if (int rc = upload(c, h, &B.blur, T)) return rc;
+            if (int rc = upload_param(c, P, nm, (size_t)C * 9, &B.blur, T)) return rc;
         }
         snprintf(nm, sizeof nm, "%d_conv_2", R);
         if (int rc = get_std(c, nm, &std)) return rc;
         NEED(P, std::string(nm) + "_weight", (size_t)C * C * 9, &w);
-        h = pack_conv3(w, C, C, std, us, 1.0f);
-        if (int rc = upload_mfma(c, h, &B.w2, T)) return rc;
+        if (int rc = upload_pack(c, gsa_pack_conv3, w, C, C, 9, std, us, &B.w2, T)) return rc;
         B.w2u = nullptr;
-        if (wino_layer(c, R, C)) {
-            h = wino43_layer(c, R, C, C) ? pack_wino43(w, C, C, std, us, 1.0f) : pack_wino(w, C, C, std, us, 1.0f);
-            if (int rc = upload(c, h, &B.w2u, T)) return rc;
-        }
+        if (int rc = upload_wino(c, w, C, C, R, true, std, us, &B.w2u, T)) return rc;
         for (int k = 0; k < 2; ++k) {
             snprintf(nm, sizeof nm, "%d_noise_%d_scale_factors", R, k + 1);
-            NEED(P, nm, (size_t)C, &w); h.assign(w, w + C);
-            if (int rc = upload(c, h, &B.nscale[k], T)) return rc;
+            if (int rc = upload_param(c, P, nm, (size_t)C, &B.nscale[k], T)) return rc;
             snprintf(nm, sizeof nm, "%d_bias_%d_bias", R, k + 1);
-            NEED(P, nm, (size_t)C, &w); h.assign(w, w + C);
-            if (int rc = upload(c, h, &B.nbias[k], T)) return rc;
+            if (int rc = upload_param(c, P, nm, (size_t)C, &B.nbias[k], T)) return rc;
             snprintf(nm, sizeof nm, "%d_adain_%d_norm_gamma", R, k + 1);
-            NEED(P, nm, (size_t)C, &w); h.assign(w, w + C);
-            if (int rc = upload(c, h, &B.gamma[k], T)) return rc;
+            if (int rc = upload_param(c, P, nm, (size_t)C, &B.gamma[k], T)) return rc;
             snprintf(nm, sizeof nm, "%d_adain_%d_norm_beta", R, k + 1);
-            NEED(P, nm, (size_t)C, &w); h.assign(w, w + C);
-            if (int rc = upload(c, h, &B.beta[k], T)) return rc;
+            if (int rc = upload_param(c, P, nm, (size_t)C, &B.beta[k], T)) return rc;
             snprintf(nm, sizeof nm, "%d_adain_%d_dense_affine", R, k + 1);
             if (int rc = get_std(c, nm, &std)) return rc;
             NEED(P, std::string(nm) + "_weight", (size_t)2 * C * L, &w);
             NEED(P, std::string(nm) + "_bias", (size_t)2 * C, &b);
             B.style_off[k] = col;
             for (int j = 0; j < 2 * C; ++j) {
-                for (int q = 0; q < L; ++q) swt[(size_t)q * J + col + j] = eff(w[(size_t)j * L + q], std, us, 1.0f);
+                for (int q = 0; q < L; ++q) swt[(size_t)q * J + col + j] = gsa_eff(w[(size_t)j * L + q], std, us, 1.0f);
                 sb[col + j] = b[j] * 1.0f;
                 col_layer[col + j] = 2 * l + k;
             }
@@ -748,13 +576,7 @@ int gsa_generator_commit(gsa_ctx* c) {
     }
     if (int rc = upload(c, swt, &c->style_wt, T)) return rc;
     if (int rc = upload(c, sb, &c->style_b, T)) return rc;
-    {
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, sizeof(int) * J));
-        T.push_back(d);
-        HIP_TRY(hipMemcpy(d, col_layer.data(), sizeof(int) * J, hipMemcpyHostToDevice));
-        c->style_col_layer = (int*)d;
-    }
+    if (int rc = upload(c, col_layer, &c->style_col_layer, T)) return rc;
     {
         // workgroups of the dlatents style kernel: each holds up to 64 columns of ONE layer (layer l = 2*level + k, 2C columns from style_off)
         std::vector<int4> tiles;
@@ -762,11 +584,7 @@ int gsa_generator_commit(gsa_ctx* c) {
             for (int k = 0; k < 2; ++k)
                 for (int c0 = 0; c0 < 2 * c->blk[l].C; c0 += 64)
                     tiles.push_back(make_int4(2 * l + k, c->blk[l].style_off[k] + c0, std::min(64, 2 * c->blk[l].C - c0), 0));
-        void* d = nullptr;
-        HIP_TRY(hipMalloc(&d, sizeof(int4) * tiles.size()));
-        T.push_back(d);
-        HIP_TRY(hipMemcpy(d, tiles.data(), sizeof(int4) * tiles.size(), hipMemcpyHostToDevice));
-        c->style_tiles = (int4*)d;
+        if (int rc = upload(c, tiles, &c->style_tiles, T)) return rc;
         c->style_num_tiles = (int)tiles.size();
     }
     {
@@ -776,10 +594,9 @@ int gsa_generator_commit(gsa_ctx* c) {
         NEED(P, std::string(nm) + "_weight", (size_t)nc * C, &w);
         NEED(P, std::string(nm) + "_bias", (size_t)nc, &b);
         h.assign((size_t)nc * C, 0.f);
-        for (size_t i = 0; i < (size_t)nc * C; ++i) h[i] = eff(w[i], std, us, 1.0f);
+        for (size_t i = 0; i < (size_t)nc * C; ++i) h[i] = gsa_eff(w[i], std, us, 1.0f);
         if (int rc = upload(c, h, &c->rgb_w, T)) return rc;
-        h.assign(b, b + nc);
-        if (int rc = upload(c, h, &c->rgb_b, T)) return rc;
+        if (int rc = upload(c, b, (size_t)nc, &c->rgb_b, T)) return rc;
     }
     c->g_ready = true;
     return GSA_OK;
@@ -826,10 +643,7 @@ static int load_bn(gsa_ctx* c, const std::string& prefix, int C, const float* bi
         NEED(c->dparams, prefix + ".beta", (size_t)C, &b);
         NEED(c->dparams, prefix + ".running_mean", (size_t)C, &m);
         NEED(c->dparams, prefix + ".running_var", (size_t)C, &v);
-        for (int i = 0; i < C; ++i) {
-            hs[i] = g[i] / std::sqrt(v[i] + 1e-5f);   // fp32: sqrtf, then one division
-            hk[i] = std::fmaf(bias[i] - m[i], hs[i], b[i]);
-        }
+        gsa_pack_bn_fold(g, b, m, v, bias, C, hs.data(), hk.data());
     }
     if (int rc = upload(c, hs, s, c->d_allocs)) return rc;
     return upload(c, hk, k, c->d_allocs);
@@ -856,13 +670,9 @@ int gsa_decoder_commit(gsa_ctx* c) {
         snprintf(nm, sizeof nm, "cvt_block_%d.0", i);
         NEED(P, std::string(nm) + ".weight", (size_t)d.F * d.I * 9, &w);
         NEED(P, std::string(nm) + ".bias", (size_t)d.F, &b);
-        h = pack_conv3(w, d.F, d.I, 1.0f, false, 1.0f);
-        if (int rc = upload_mfma(c, h, &d.cvt_w, T)) return rc;
+        if (int rc = upload_pack(c, gsa_pack_conv3, w, d.F, d.I, 9, 1.0f, false, &d.cvt_w, T)) return rc;
         d.cvt_u = d.b_u = nullptr;
-        if (wino_layer(c, 4 << i, d.F)) {
-            h = wino43_layer(c, 4 << i, d.I, d.F) ? pack_wino43(w, d.F, d.I, 1.0f, false, 1.0f) : pack_wino(w, d.F, d.I, 1.0f, false, 1.0f);
-            if (int rc = upload(c, h, &d.cvt_u, T)) return rc;
-        }
+        if (int rc = upload_wino(c, w, d.F, d.I, 4 << i, true, 1.0f, false, &d.cvt_u, T)) return rc;
         snprintf(nm, sizeof nm, "cvt_block_%d.1", i);
         if (int rc = load_bn(c, nm, d.F, b, &d.cvt_s, &d.cvt_beta)) return rc;
         if (!d.is_last) {
@@ -870,36 +680,31 @@ int gsa_decoder_commit(gsa_ctx* c) {
             const std::string pf = "main_block_" + std::to_string(i) + ".1.base_layers";
             NEED(P, pf + ".0.weight", (size_t)d.cs * d.in_c * 9, &w);
             NEED(P, pf + ".0.bias", (size_t)d.cs, &b);
-            h = (8 << i) >= 16 ? pack_upconv(w, d.cs, d.in_c, 1.0f, false, 1.0f) : pack_conv3(w, d.cs, d.in_c, 1.0f, false, 1.0f);
-            if (int rc = upload_mfma(c, h, &d.a_w, T)) return rc;
+            if (int rc = (8 << i) >= 16 ? upload_pack(c, gsa_pack_upconv, w, d.cs, d.in_c, 16, 1.0f, false, &d.a_w, T)
+                                        : upload_pack(c, gsa_pack_conv3, w, d.cs, d.in_c, 9, 1.0f, false, &d.a_w, T)) return rc;
             if (int rc = load_bn(c, pf + ".1", d.cs, b, &d.a_s, &d.a_beta)) return rc;
             NEED(P, pf + "." + std::to_string(second) + ".weight", (size_t)d.cs * d.cs * 9, &w);
             NEED(P, pf + "." + std::to_string(second) + ".bias", (size_t)d.cs, &b);
-            h = pack_conv3(w, d.cs, d.cs, 1.0f, false, 1.0f);
-            if (int rc = upload_mfma(c, h, &d.b_w, T)) return rc;
-            if (wino_layer(c, 8 << i, d.cs)) {
-                h = pack_wino(w, d.cs, d.cs, 1.0f, false, 1.0f);      // conv b carries the residual: never the F(4x4,3x3) form (conv_uses_wino43)
-                if (int rc = upload(c, h, &d.b_u, T)) return rc;
-            }
+            if (int rc = upload_pack(c, gsa_pack_conv3, w, d.cs, d.cs, 9, 1.0f, false, &d.b_w, T)) return rc;
+            // conv b carries the residual: never the F(4x4,3x3) form (conv_uses_wino43)
+            if (int rc = upload_wino(c, w, d.cs, d.cs, 8 << i, false, 1.0f, false, &d.b_u, T)) return rc;
             if (int rc = load_bn(c, pf + "." + std::to_string(second + 1), d.cs, b, &d.b_s, &d.b_beta)) return rc;
             d.has_sc = d.cs != d.in_c;
             if (d.has_sc) {
                 const std::string sc = "main_block_" + std::to_string(i) + ".1.shortcut.0";
                 NEED(P, sc + ".weight", (size_t)d.cs * d.in_c, &w);
                 NEED(P, sc + ".bias", (size_t)d.cs, &b);
-                h = pack_conv1(w, d.cs, d.in_c);
+                h.resize((size_t)d.cs * d.in_c); gsa_pack_conv1(w, d.cs, d.in_c, h.data());
                 if (int rc = upload_mfma(c, h, &d.sc_w, T)) return rc;
-                h.assign(b, b + d.cs);
-                if (int rc = upload(c, h, &d.sc_b, T)) return rc;
+                if (int rc = upload(c, b, (size_t)d.cs, &d.sc_b, T)) return rc;
             }
         } else {
             const std::string pf = "main_block_" + std::to_string(i) + ".0";
             NEED(P, pf + ".weight", (size_t)d.cs * d.in_c * 9, &w);
             NEED(P, pf + ".bias", (size_t)d.cs, &b);
-            h = pack_final(w, d.cs, d.in_c);
+            h.resize((size_t)d.cs * d.in_c * 9); gsa_pack_final(w, d.cs, d.in_c, h.data());
             if (int rc = upload(c, h, &d.f_w, T)) return rc;
-            h.assign(b, b + d.cs);
-            if (int rc = upload(c, h, &d.f_b, T)) return rc;
+            if (int rc = upload(c, b, (size_t)d.cs, &d.f_b, T)) return rc;
         }
     }
     c->d_ready = true;
@@ -972,12 +777,9 @@ int gsa_reserve(gsa_ctx* c, int32_t max_batch) {
         for (int i = 0; i < 2; ++i)
             if (int rc = dev_alloc(c, N * L, &c->lat[i], T)) return rc;
         if (int rc = dev_alloc(c, N * c->style_cols, &c->styles, T)) return rc;
-        if (int rc = dev_alloc(c, 2 + kMapSlices, &c->map_ctl, T)) return rc;
-        HIP_TRY(hipMemset(c->map_ctl, 0, (2 + kMapSlices) * sizeof(unsigned)));
-        for (int i = 0; i < 2; ++i) {
-            if (int rc = dev_alloc(c, N * L, &c->map_ll[i], T)) return rc;
-            HIP_TRY(hipMemset(c->map_ll[i], 0, N * L * sizeof(unsigned long long)));     // tag 0 never matches a launch
-        }
+        if (int rc = dev_alloc_zeroed(c, 2 + kMapSlices, &c->map_ctl, T)) return rc;
+        for (int i = 0; i < 2; ++i)
+            if (int rc = dev_alloc_zeroed(c, N * L, &c->map_ll[i], T)) return rc;     // tag 0 never matches a launch
         size_t maxact = 0;
         int maxC = 0;
         for (int l = 0; l < c->nlev; ++l) {
@@ -994,21 +796,16 @@ int gsa_reserve(gsa_ctx* c, int32_t max_batch) {
         if (int rc = dev_alloc(c, N * maxact, &c->x1, T)) return rc;
         if (int rc = dev_alloc(c, N * maxC, &c->aff1, T)) return rc;
         prow_elems = std::max(prow_elems, (size_t)64 * maxC);
-        if (int rc = dev_alloc(c, N * prow_elems, &c->partials, T)) return rc;
+        // all zero between layers: finalize_kernel clears what it read
+        if (int rc = dev_alloc_zeroed(c, N * prow_elems, &c->partials, T)) return rc;
         c->partials_bytes = N * prow_elems * sizeof(StatPart);
         c->stat_acc_bytes = N * maxC * sizeof(StatPart);
         c->ticket_bytes = N * ((maxC + 63) / 64) * sizeof(unsigned);
         c->stats_dirty = false;
-        HIP_TRY(hipMemset(c->partials, 0, N * prow_elems * sizeof(StatPart)));     // all zero between layers: finalize_kernel clears what it read
-        if (int rc = dev_alloc(c, N * maxC, &c->stat_acc, T)) return rc;
-        HIP_TRY(hipMemset(c->stat_acc, 0, N * maxC * sizeof(StatPart)));
-        if (int rc = dev_alloc(c, N * ((maxC + 63) / 64), &c->stat_tickets, T)) return rc;
-        HIP_TRY(hipMemset(c->stat_tickets, 0, N * ((maxC + 63) / 64) * sizeof(unsigned)));
+        if (int rc = dev_alloc_zeroed(c, N * maxC, &c->stat_acc, T)) return rc;
+        if (int rc = dev_alloc_zeroed(c, N * ((maxC + 63) / 64), &c->stat_tickets, T)) return rc;
     }
-    {
-        if (int rc = dev_alloc(c, 16, &c->stamps, T)) return rc;
-        HIP_TRY(hipMemset(c->stamps, 0, 16 * sizeof(unsigned long long)));
-    }
+    if (int rc = dev_alloc_zeroed(c, 16, &c->stamps, T)) return rc;
     if (c->d_ready) {
         for (int i = c->d_s0; i < c->d_n; ++i) {
             const DecLevelDev& d = c->dl[i];
@@ -1029,30 +826,14 @@ int gsa_reserve(gsa_ctx* c, int32_t max_batch) {
 
 // ------------------------------------------------------------------------ forward passes
 
-static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* dl, const float* const* noise, float* rgb,
-                              uint8_t* img, float* const* feats, bool record_levels);
+static ConvParams conv_base(const gsa_ctx* c) {      // the fields every convolution launch takes from the context
+    ConvParams cp{}; cp.stamps = c->stamps; cp.zeros = c->zeros; cp.dbg = c->dbg; cp.bf16 = c->bf16; cp.device = c->device; cp.prio = c->prio;
+    return cp;
+}
 
-// The statistics rely on `partials` / `stat_acc` / the tickets being all zero between layers (the producers ADD to their rows,
-// finalize_kernel clears what it read).  A pass that fails between a producer and its finalize (a launch error, a null noise
-// plane) would leave rows dirty and every later pass of the context would add them into its instance-norm sums: the context
-// remembers that a pass did not complete and the next one re-zeroes the three buffers on its stream first.
-// The input is either z (N, latent_size) -- mapping network, then the styles from one w row per sample -- or, with z null, the
-// untruncated per-layer dlatents dl (N, 2*nlev, latent_size), whose styles take layer l's row for layer l's columns.
-static int run_generator(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* dl, const float* const* noise, float* rgb,
-                         uint8_t* img, float* const* feats, bool record_levels = false) {
-    if (c->stats_dirty) {
-        HIP_TRY(hipMemsetAsync(c->partials, 0, c->partials_bytes, s));
-        HIP_TRY(hipMemsetAsync(c->stat_acc, 0, c->stat_acc_bytes, s));
-        HIP_TRY(hipMemsetAsync(c->stat_tickets, 0, c->ticket_bytes, s));
-    }
-    c->stats_dirty = true;
-    const int rc = run_generator_pass(c, s, n, z, dl, noise, rgb, img, feats, record_levels);
-    if (rc == GSA_OK) c->stats_dirty = false;
-    if (rc == GSA_OK && c->fault_range_after >= 0 && c->fault_range_after-- == 0) {
-        // test hook: from this pass on the statistics-range word reads as if an instance norm had overflowed (it is sticky)
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c->map_ctl, 1, 1, s));
-    }
-    return rc;
+// products per output and (input, output) channel pair a plain 3x3 conv executes in the form launch_conv3x3 picks for cp (9 direct)
+static double conv3_products(const ConvParams& cp, int epi) {
+    return conv_uses_wino43(cp, epi, false) ? 2.25 : conv_uses_wino(cp, epi, false) ? 4 : 9;
 }
 
 // mapping network: PixelNorm, 8 x (dense + LeakyReLU) of z into w (N, latent_size); the fallback chain ping-pongs through lat[0/1]
@@ -1107,7 +888,7 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
                 if (!B.has_conv1) {
                     pp.src = c->constant; pp.src_per_sample = 0; pp.blur = nullptr;
                 } else {
-                    ConvParams cp{}; cp.stamps = c->stamps; cp.zeros = c->zeros; cp.dbg = c->dbg; cp.bf16 = c->bf16; cp.device = c->device; cp.prio = c->prio;
+                    ConvParams cp = conv_base(c);
                     cp.src0 = c->x2[l - 1]; cp.aff0 = c->aff2[l - 1]; cp.C0 = Cin;
                     cp.Hs = R / 2; cp.Ws = R / 2; cp.H = R; cp.W = R;
                     cp.wpk = B.w1; cp.Cout = C; cp.out = c->t_raw;
@@ -1148,7 +929,7 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
                 HIP_TRY(launch_post(pp, n, s));
                 prow = post_rows_used(pp);
             } else {
-                ConvParams cp{}; cp.stamps = c->stamps; cp.zeros = c->zeros; cp.dbg = c->dbg; cp.bf16 = c->bf16; cp.device = c->device; cp.prio = c->prio;
+                ConvParams cp = conv_base(c);
                 cp.src0 = c->x1; cp.aff0 = c->aff1; cp.C0 = C;
                 cp.Hs = R; cp.Ws = R; cp.H = R; cp.W = R;
                 cp.wpk = B.w2; cp.wino = B.w2u; cp.Cout = C; cp.out = c->x2[l];
@@ -1161,7 +942,7 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
                     cp.fin_style = c->styles + B.style_off[1]; cp.fin_style_stride = c->style_cols;
                     cp.fin_gamma = B.gamma[1]; cp.fin_beta = B.beta[1]; cp.fin_aff = c->aff2[l]; cp.fin_flags = c->map_ctl;
                 }
-                Launch lp(c, s, layer, 2.0 * px * C * C * (conv_uses_wino43(cp, EPI_SYNTH, false) ? 2.25 : conv_uses_wino(cp, EPI_SYNTH, false) ? 4 : 9), 4.0 * (2 * px * C + px), 2.0 * px * C * C * 9);
+                Launch lp(c, s, layer, 2.0 * px * C * C * conv3_products(cp, EPI_SYNTH), 4.0 * (2 * px * C + px), 2.0 * px * C * C * 9);
                 HIP_TRY(launch_conv3x3(cp, EPI_SYNTH, false, n, s));
                 prow = rows;
                 if (fused_fin) continue;
@@ -1202,12 +983,35 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
     return GSA_OK;
 }
 
+// The statistics rely on `partials` / `stat_acc` / the tickets being all zero between layers (the producers ADD to their rows,
+// finalize_kernel clears what it read).  A pass that fails between a producer and its finalize (a launch error, a null noise
+// plane) would leave rows dirty and every later pass of the context would add them into its instance-norm sums: the context
+// remembers that a pass did not complete and the next one re-zeroes the three buffers on its stream first.
+// The input is either z (N, latent_size) -- mapping network, then the styles from one w row per sample -- or, with z null, the
+// untruncated per-layer dlatents dl (N, 2*nlev, latent_size), whose styles take layer l's row for layer l's columns.
+static int run_generator(gsa_ctx* c, hipStream_t s, int n, const float* z, const float* dl, const float* const* noise, float* rgb,
+                         uint8_t* img, float* const* feats, bool record_levels = false) {
+    if (c->stats_dirty) {
+        HIP_TRY(hipMemsetAsync(c->partials, 0, c->partials_bytes, s));
+        HIP_TRY(hipMemsetAsync(c->stat_acc, 0, c->stat_acc_bytes, s));
+        HIP_TRY(hipMemsetAsync(c->stat_tickets, 0, c->ticket_bytes, s));
+    }
+    c->stats_dirty = true;
+    const int rc = run_generator_pass(c, s, n, z, dl, noise, rgb, img, feats, record_levels);
+    if (rc == GSA_OK) c->stats_dirty = false;
+    if (rc == GSA_OK && c->fault_range_after >= 0 && c->fault_range_after-- == 0) {
+        // test hook: from this pass on the statistics-range word reads as if an instance norm had overflowed (it is sticky)
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c->map_ctl, 1, 1, s));
+    }
+    return rc;
+}
+
 // feats_nhwc[i] / feat_aff[i]: decoder inputs in kernel layout (aff may be null)
 // the cvt convolution of decoder level i (networks_seg.py:64-79): conv3x3 + bias -> BN -> LeakyReLU on feature i
 static ConvParams cvt_params(gsa_ctx* c, int i, const float* src, const Aff* aff) {
     const DecLevelDev& d = c->dl[i];
     const int R = 4 << i;
-    ConvParams cp{}; cp.stamps = c->stamps; cp.zeros = c->zeros; cp.dbg = c->dbg; cp.bf16 = c->bf16; cp.device = c->device; cp.prio = c->prio;
+    ConvParams cp = conv_base(c);
     cp.src0 = src; cp.aff0 = aff; cp.C0 = d.I;
     cp.Hs = R; cp.Ws = R; cp.H = R; cp.W = R;
     cp.wpk = d.cvt_w; cp.wino = d.cvt_u; cp.Cout = d.F; cp.out = c->cvt[i];
@@ -1237,7 +1041,7 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
             if (with_rgb) { cp.rgb_w = c->rgb_w; cp.rgb_b = c->rgb_b; cp.rgb_img = rgb_img; }
             snprintf(layer, sizeof layer, with_rgb ? "d.cvt_%d+torgb" : "d.cvt_%d", i);
             Launch lp(c, s, layer,
-                      2.0 * px * d.F * d.I * (conv_uses_wino43(cp, EPI_DEC, false) ? 2.25 : conv_uses_wino(cp, EPI_DEC, false) ? 4 : 9) + (with_rgb ? 2.0 * px * d.I * nc : 0.0),
+                      2.0 * px * d.F * d.I * conv3_products(cp, EPI_DEC) + (with_rgb ? 2.0 * px * d.I * nc : 0.0),
                       4.0 * px * (d.I + d.F) + (with_rgb ? px * nc : 0.0), 2.0 * px * d.F * d.I * 9 + (with_rgb ? 2.0 * px * d.I * nc : 0.0));
             HIP_TRY(launch_conv3x3(cp, EPI_DEC, false, n, s));
         }
@@ -1245,7 +1049,7 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
             const int R2 = 2 * R;
             const double px2 = 4 * px;
             {   // ResBlock conv a (+ fused 1x1 shortcut) on nearest-x2(concat(prev, cvt))
-                ConvParams cp{}; cp.stamps = c->stamps; cp.zeros = c->zeros; cp.dbg = c->dbg; cp.bf16 = c->bf16; cp.device = c->device; cp.prio = c->prio;
+                ConvParams cp = conv_base(c);
                 if (i > s0) { cp.src0 = c->prev[i - 1]; cp.C0 = d.F; cp.src1 = c->cvt[i]; cp.C1 = d.F; }
                 else { cp.src0 = c->cvt[i]; cp.C0 = d.F; }
                 cp.Hs = R; cp.Ws = R; cp.up = 1; cp.H = R2; cp.W = R2;
@@ -1265,7 +1069,7 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
                 }
             }
             {   // ResBlock conv b, + shortcut
-                ConvParams cp{}; cp.stamps = c->stamps; cp.zeros = c->zeros; cp.dbg = c->dbg; cp.bf16 = c->bf16; cp.device = c->device; cp.prio = c->prio;
+                ConvParams cp = conv_base(c);
                 cp.src0 = c->ya[i]; cp.C0 = d.cs;
                 cp.Hs = R2; cp.Ws = R2; cp.H = R2; cp.W = R2;
                 cp.wpk = d.b_w; cp.wino = d.b_u; cp.Cout = d.cs; cp.out = c->prev[i];
@@ -1274,7 +1078,7 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
                 else if (i == s0) { cp.resid = c->cvt[i]; cp.resid_up = 1; }   // identity shortcut: the upsampled input itself
                 else { cp.resid = c->prev[i - 1]; cp.resid1 = c->cvt[i]; cp.res_c0 = d.F; cp.resid_up = 1; }   // ... over concat(prev, cvt)
                 snprintf(layer, sizeof layer, "d.main_%d.b", i);
-                Launch lp(c, s, layer, 2.0 * px2 * d.cs * d.cs * (conv_uses_wino43(cp, EPI_DEC, false) ? 2.25 : conv_uses_wino(cp, EPI_DEC, false) ? 4 : 9), 4.0 * px2 * d.cs * 3, 2.0 * px2 * d.cs * d.cs * 9);
+                Launch lp(c, s, layer, 2.0 * px2 * d.cs * d.cs * conv3_products(cp, EPI_DEC), 4.0 * px2 * d.cs * 3, 2.0 * px2 * d.cs * d.cs * 9);
                 HIP_TRY(launch_conv3x3(cp, EPI_DEC, false, n, s));
             }
         } else if (factor > 1) {
@@ -1305,10 +1109,15 @@ static int check_dlatents(gsa_ctx* c, const float* dl, int32_t num_layers) {
     return GSA_OK;
 }
 
-static int generator_forward(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* dl, const float* const* noise,
-                             int32_t num_noise, float* rgb, uint8_t* img, float* const* feats, int32_t num_feats) {
+static int check_noise(gsa_ctx* c, const float* const* noise, int32_t num_noise) {
     if (!noise) return fail(c, GSA_ERR_INVALID, "noise must not be null");
     if (num_noise != 2 * c->nlev) return fail(c, GSA_ERR_INVALID, "%d noise planes passed, this generator has %d", num_noise, 2 * c->nlev);
+    return GSA_OK;
+}
+
+static int generator_forward(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* dl, const float* const* noise,
+                             int32_t num_noise, float* rgb, uint8_t* img, float* const* feats, int32_t num_feats) {
+    if (int rc = check_noise(c, noise, num_noise)) return rc;
     if (feats && num_feats != c->nlev) return fail(c, GSA_ERR_INVALID, "%d feature pointers passed, this generator yields %d", num_feats, c->nlev);
     if (int rc = check_batch(c, n)) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -1363,8 +1172,7 @@ int gsa_decoder_forward(gsa_ctx* c, void* stream, int32_t n, const float* const*
 // instead of riding on the last cvt convolution, and the final conv reduces the logits per block
 static int generate(gsa_ctx* c, void* stream, int32_t n, const float* z, const float* dl, const float* const* noise, int32_t num_noise,
                     uint8_t* img, uint8_t* mask, int factor = 1) {
-    if (!noise) return fail(c, GSA_ERR_INVALID, "noise must not be null");
-    if (num_noise != 2 * c->nlev) return fail(c, GSA_ERR_INVALID, "%d noise planes passed, this generator has %d", num_noise, 2 * c->nlev);
+    if (int rc = check_noise(c, noise, num_noise)) return rc;
     if (c->d_n != c->nlev) return fail(c, GSA_ERR_INVALID, "decoder expects %d features, the generator yields %d", c->d_n, c->nlev);
     for (int l = 0; l < c->nlev; ++l)
         if (c->d_inch[l] != c->ch[l]) return fail(c, GSA_ERR_INVALID, "decoder in_channels[%d]=%d but the generator feature has %d", l, c->d_inch[l], c->ch[l]);

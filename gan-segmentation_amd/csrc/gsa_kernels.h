@@ -90,6 +90,12 @@ struct FinalizeParams {
 hipError_t launch_conv3x3(const ConvParams& p, int epi, bool shortcut, int n, hipStream_t s);
 bool conv_uses_ws(const ConvParams& p, int epi, bool shortcut, int n);
 bool conv_uses_ksplit(const ConvParams& p, bool shortcut);         // true: 4-way K split form (static rule: layer shape only)
+// The static shape rule of the Winograd forms, stated once: the commit (gsa_api.cpp) packs U by it, conv_uses_wino / conv_uses_wino43
+// select the kernel by it plus the clauses only a launch knows.  F(2x2,3x3): fp32 mode, outputs >= 64 px, or >= 32 px with >= 64 output
+// channels, or >= 16 px with >= 256 (fewer tiles leave the chip idle: the direct small-tile kernels are faster there).  F(4x4,3x3): such
+// a layer with >= 64 input channels and >= 32 px.  The oracle's copy (oracle/c/gsa_oracle.c use_wino, use_wino43) stays separate on purpose.
+inline bool wino_shape(int H, int Cout, int bf16) { return !bf16 && (H >= 64 || (H >= 32 && Cout >= 64) || (H >= 16 && Cout >= 256)); }
+inline bool wino43_shape(int H, int Cin) { return Cin >= 64 && H >= 32; }
 bool conv_uses_wino43(const ConvParams& p, int epi, bool shortcut); // true: Winograd F(4x4,3x3) form (static rule: layer shape only; p.wino then holds the 36-frequency panel)
 bool wino43_enabled();                                              // GSA_WINO43 != 0
 bool conv_uses_wino(const ConvParams& p, int epi, bool shortcut);   // true: Winograd form (static rule: layer shape only)   // true: wave-specialised kernel, no partial rows

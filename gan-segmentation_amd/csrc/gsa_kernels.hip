@@ -1008,12 +1008,14 @@ __global__ __launch_bounds__(256 * PS) void conv3x3_ksplit(ConvParams p) {
     act_store4<BF>(p.out, ((size_t)(n * p.H + y) * p.W + xb + xj) * p.Cout + g * 16 + cq4, vt);
 }
 
-// Packed fp32 adds for the Winograd transforms: one v_pk_add_f32 per two additions (neg modifiers for a subtraction; the
-// same IEEE results).  hipcc scalarises a <4 x float> add whose only users are element extracts -- each component feeds its
-// own MFMA -- into four v_add_f32 / v_sub_f32 (and folds every other spelling of the subtraction back into one), so the
-// instruction is written out.  f32 MFMAs and vector-ALU instructions share the SIMD's issue time:
-// every instruction saved is MFMA time gained.
-// Hazards: the compiler's hazard recot form needs 144.  Canonical arithmetic: oracle/c/gsa_oracle.c conv3x3_wino (the transforms
+// ------------------------------------------------------------------------------------------
+// conv3x3 (pad 1, stride 1, one source) in WINOGRAD F(2x2, 3x3) form on v_mfma_f32_16x16x4_f32.
+//
+//     Y = A^T [ sum_c (G g_c G^T) .* (B^T d_c B) ] A      per 2x2 output tile: 16 products per (tile, c, o) instead of 36
+//
+// The sixteen "frequencies" f = 4i+j are sixteen independent GEMMs  M_f[tile][o] = sum_c V_f[tile][c] U_f[c][o]:
+// M = 16 Winograd tiles, N = 16 output channels, K = input channels -- 64 MFMAs per 16-channel block and 64 output
+// pixels where the direct form needs 144.  Canonical arithmetic: oracle/c/gsa_oracle.c conv3x3_wino (the transforms
 // are plain fp32 adds in a fixed order, each M_f is one k-ordered fmaf chain = the MFMA, U is computed in double on
 // the host and rounded once), so the result is reproduced BIT FOR BIT; DESIGN.md states the rule that selects the
 // form (layer shape only: plain 3x3 convs with outputs >= 32 px, fp32 mode).
@@ -3946,11 +3948,12 @@ static hipError_t launch_ksplit(const ConvParams& p, int epi, int n, hipStream_t
 
 // ---- Winograd form ---------------------------------------------------------------------------------------
 // The rule is static (layer shape and arithmetic mode only, never the batch size): it is part of the canonical
-// arithmetic and the oracle applies the same one (oracle/c/gsa_oracle.c use_wino).
+// arithmetic and the oracle applies the same one (oracle/c/gsa_oracle.c use_wino).  Its shape clause is wino_shape (gsa_kernels.h),
+// which the commit packs U by: a layer that passes it always has p.wino.
 bool conv_uses_wino(const ConvParams& p, int epi, bool sc) {
     static const bool enabled = !(getenv("GSA_WINO") && atoi(getenv("GSA_WINO")) == 0);
-    return enabled && p.wino != nullptr && !p.bf16 && !sc && !p.up && p.src1 == nullptr && p.C1 == 0 && epi != EPI_RAW &&
-           (p.H >= 64 || (p.H >= 32 && p.Cout >= 64) || (p.H >= 16 && p.Cout >= 256)) && p.H == p.W && p.H % 16 == 0 && p.Cout % 16 == 0 && p.C0 % 16 == 0;
+    return enabled && p.wino != nullptr && !sc && !p.up && p.src1 == nullptr && p.C1 == 0 && epi != EPI_RAW &&
+           wino_shape(p.H, p.Cout, p.bf16) && p.H == p.W && p.H % 16 == 0 && p.Cout % 16 == 0 && p.C0 % 16 == 0;
 }
 
 // output channels per workgroup = 16*NT.  NT = 2 (one workgroup per CU with the whole register file, the input transform and
@@ -4015,7 +4018,7 @@ bool wino43_enabled() {
     return enabled;
 }
 bool conv_uses_wino43(const ConvParams& p, int epi, bool sc) {
-    return wino43_enabled() && conv_uses_wino(p, epi, sc) && p.C0 >= 64 && p.H >= 32 && p.resid == nullptr;
+    return wino43_enabled() && conv_uses_wino(p, epi, sc) && wino43_shape(p.H, p.C0) && p.resid == nullptr;
 }
 
 template <int EPI>
