@@ -436,9 +436,9 @@ int gsa_create(int device, gsa_ctx** out) {
         delete c;
         return rc;
     }
-    if (const char* v = getenv("GSA_SIDE_LEVELS")) c->side_levels = atoi(v);
-    if (const char* v = getenv("GSA_DBG")) c->dbg = atoi(v);
-    if (const char* v = getenv("GSA_PRIO")) c->prio = atoi(v);
+    c->side_levels = env_int("GSA_SIDE_LEVELS", c->side_levels);
+    c->dbg = env_int("GSA_DBG", c->dbg);
+    c->prio = env_int("GSA_PRIO", c->prio);
     *out = c;
     return GSA_OK;
 }
@@ -686,7 +686,7 @@ int gsa_decoder_commit(gsa_ctx* c) {
             NEED(P, pf + "." + std::to_string(second) + ".weight", (size_t)d.cs * d.cs * 9, &w);
             NEED(P, pf + "." + std::to_string(second) + ".bias", (size_t)d.cs, &b);
             if (int rc = upload_pack(c, gsa_pack_conv3, w, d.cs, d.cs, 9, 1.0f, false, &d.b_w, T)) return rc;
-            // conv b carries the residual: never the F(4x4,3x3) form (conv_uses_wino43)
+            // conv b carries the residual: never the F(4x4,3x3) form (ConvForm::Wino43 needs a layer without one)
             if (int rc = upload_wino(c, w, d.cs, d.cs, 8 << i, false, 1.0f, false, &d.b_u, T)) return rc;
             if (int rc = load_bn(c, pf + "." + std::to_string(second + 1), d.cs, b, &d.b_s, &d.b_beta)) return rc;
             d.has_sc = d.cs != d.in_c;
@@ -749,8 +749,7 @@ int gsa_status_snapshot(gsa_ctx* c, void* stream, uint32_t* host_words) {
 int gsa_debug_inject(gsa_ctx* c, int32_t kind, int32_t arg) {
     if (!c) return GSA_ERR_INVALID;
     // doubly gated: the explicit call AND GSA_TEST_HOOKS=1 in the environment of the process (the tests set it; neither alone arms anything)
-    const char* hooks = getenv("GSA_TEST_HOOKS");
-    if (!hooks || atoi(hooks) != 1) return fail(c, GSA_ERR_STATE, "gsa_debug_inject: test hooks are off (GSA_TEST_HOOKS=1 enables them)");
+    if (env_int("GSA_TEST_HOOKS", 0) != 1) return fail(c, GSA_ERR_STATE, "gsa_debug_inject: test hooks are off (GSA_TEST_HOOKS=1 enables them)");
     switch (kind) {
     case 0: c->fault = 0; c->fault_range_after = -1; return GSA_OK;
     case 1: case 2: c->fault = kind; return GSA_OK;
@@ -829,11 +828,6 @@ int gsa_reserve(gsa_ctx* c, int32_t max_batch) {
 static ConvParams conv_base(const gsa_ctx* c) {      // the fields every convolution launch takes from the context
     ConvParams cp{}; cp.stamps = c->stamps; cp.zeros = c->zeros; cp.dbg = c->dbg; cp.bf16 = c->bf16; cp.device = c->device; cp.prio = c->prio;
     return cp;
-}
-
-// products per output and (input, output) channel pair a plain 3x3 conv executes in the form launch_conv3x3 picks for cp (9 direct)
-static double conv3_products(const ConvParams& cp, int epi) {
-    return conv_uses_wino43(cp, epi, false) ? 2.25 : conv_uses_wino(cp, epi, false) ? 4 : 9;
 }
 
 // mapping network: PixelNorm, 8 x (dense + LeakyReLU) of z into w (N, latent_size); the fallback chain ping-pongs through lat[0/1]
@@ -938,11 +932,12 @@ static int run_generator_pass(gsa_ctx* c, hipStream_t s, int n, const float* z, 
                 int rows = conv_stat_rows(R, R, C, n);
                 cp.stat_rows_host = &rows;            // the launcher reports the partial rows it used
                 const bool fused_fin = conv_fuses_finalize(cp, EPI_SYNTH, false);
+                const double products = conv_form_products(conv3x3_form(cp, EPI_SYNTH, false));
                 if (fused_fin) {                      // the workgroup holds the whole plane: it writes the coefficients itself, no finalize launch
                     cp.fin_style = c->styles + B.style_off[1]; cp.fin_style_stride = c->style_cols;
                     cp.fin_gamma = B.gamma[1]; cp.fin_beta = B.beta[1]; cp.fin_aff = c->aff2[l]; cp.fin_flags = c->map_ctl;
                 }
-                Launch lp(c, s, layer, 2.0 * px * C * C * conv3_products(cp, EPI_SYNTH), 4.0 * (2 * px * C + px), 2.0 * px * C * C * 9);
+                Launch lp(c, s, layer, 2.0 * px * C * C * products, 4.0 * (2 * px * C + px), 2.0 * px * C * C * 9);
                 HIP_TRY(launch_conv3x3(cp, EPI_SYNTH, false, n, s));
                 prow = rows;
                 if (fused_fin) continue;
@@ -1041,7 +1036,7 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
             if (with_rgb) { cp.rgb_w = c->rgb_w; cp.rgb_b = c->rgb_b; cp.rgb_img = rgb_img; }
             snprintf(layer, sizeof layer, with_rgb ? "d.cvt_%d+torgb" : "d.cvt_%d", i);
             Launch lp(c, s, layer,
-                      2.0 * px * d.F * d.I * conv3_products(cp, EPI_DEC) + (with_rgb ? 2.0 * px * d.I * nc : 0.0),
+                      2.0 * px * d.F * d.I * conv_form_products(conv3x3_form(cp, EPI_DEC, false)) + (with_rgb ? 2.0 * px * d.I * nc : 0.0),
                       4.0 * px * (d.I + d.F) + (with_rgb ? px * nc : 0.0), 2.0 * px * d.F * d.I * 9 + (with_rgb ? 2.0 * px * d.I * nc : 0.0));
             HIP_TRY(launch_conv3x3(cp, EPI_DEC, false, n, s));
         }
@@ -1078,7 +1073,7 @@ static int run_decoder(gsa_ctx* c, hipStream_t s, int n, const float* const* fsr
                 else if (i == s0) { cp.resid = c->cvt[i]; cp.resid_up = 1; }   // identity shortcut: the upsampled input itself
                 else { cp.resid = c->prev[i - 1]; cp.resid1 = c->cvt[i]; cp.res_c0 = d.F; cp.resid_up = 1; }   // ... over concat(prev, cvt)
                 snprintf(layer, sizeof layer, "d.main_%d.b", i);
-                Launch lp(c, s, layer, 2.0 * px2 * d.cs * d.cs * conv3_products(cp, EPI_DEC), 4.0 * px2 * d.cs * 3, 2.0 * px2 * d.cs * d.cs * 9);
+                Launch lp(c, s, layer, 2.0 * px2 * d.cs * d.cs * conv_form_products(conv3x3_form(cp, EPI_DEC, false)), 4.0 * px2 * d.cs * 3, 2.0 * px2 * d.cs * d.cs * 9);
                 HIP_TRY(launch_conv3x3(cp, EPI_DEC, false, n, s));
             }
         } else if (factor > 1) {

@@ -379,7 +379,7 @@ using namespace lean;
 // the layers this file takes in bf16 mode: plain 3x3 convolutions from 32 px on, one source of a multiple of 16 channels up to 512, synthesis
 // epilogue with direct statistics or decoder epilogue with the residual absent or one half-resolution tensor.  GSA_BF16_LEAN=0: conv3x3_mfma.
 bool bf16_lean_applies(const ConvParams& p, int epi, bool sc) {
-    static const bool enabled = !(getenv("GSA_BF16_LEAN") && atoi(getenv("GSA_BF16_LEAN")) == 0);
+    static const bool enabled = env_int("GSA_BF16_LEAN", 1) != 0;
     if (!enabled || !p.bf16 || sc || p.up || p.C1 != 0 || p.src1 != nullptr) return false;
     if (p.H != p.W || p.H % 16 || p.H < 32 || p.Hs != p.H || p.C0 % 16 || p.C0 > 512 || p.Cout % 16) return false;
     if (epi == EPI_SYNTH) return p.partials != nullptr && p.noise != nullptr && p.fin_aff == nullptr && p.resid == nullptr;

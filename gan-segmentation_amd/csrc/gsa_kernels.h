@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <atomic>
 #include <string>
@@ -34,7 +35,7 @@ struct ConvParams {
     int H, W;        // output size
     const float* wpk;   // packed weights [Cout/16][Cin/16][tap][ci][16][cg]
     const float* wino;  // or null: the same conv in Winograd F(2x2,3x3) form, U packed [Cout/16][Cin/16][f16][ci][16][cg]
-                        // (F(4x4,3x3) layers, conv_uses_wino43: [Cout/16][Cin/8][f36][kq][16][2], channel 8b + 2kq + j)
+                        // (F(4x4,3x3) layers, ConvForm::Wino43: [Cout/16][Cin/8][f36][kq][16][2], channel 8b + 2kq + j)
     int Cout;           // total output channels
     float* out;         // NHWC
     // EPI_SYNTH: AddNoise -> Bias -> LeakyReLU -> statistics
@@ -49,7 +50,8 @@ struct ConvParams {
     const float* wsc; const float* sc_bias; float* out_sc;
     int tiles_x, tiles_y, groups, total_tiles;   // filled by the launcher
     int stats_direct;                            // filled by the launcher: EPI_SYNTH sums go to acc with atomics (no partial rows)
-    int* stat_rows_host;                         // host pointer or null: the launcher reports the partial rows it used (0 = direct)
+    int* stat_rows_host;                         // host pointer or null: the launcher reports the partial rows it used (0 = direct).  A host pointer has
+                                                 // no business in a kernel argument; it stays because moving a field changes the argument layout of every kernel
     int w_resident;                              // filled by the launcher: whole weight panel LDS-resident (conv3x3 DB form)
     int group_minor;                             // filled by the launcher (conv3x3_wino): 1-D grid, the channel groups of a tile consecutive on one XCD
     unsigned long long* stamps;   // diagnostic build (-DGSA_STAMP) only: per-phase cycle sums
@@ -86,19 +88,33 @@ struct FinalizeParams {
     unsigned* flags;   // sticky device word or null: set to 1 when a sum is within a factor 4 of its 64-bit wrap or the variance is negative
 };
 
+// One reader for the GSA_* switches: atoi of the variable, or dflt when it is unset (set but not a number reads as 0, as atoi does).
+// Each site keeps the value in a static const of its own; INTEGRATION.md lists every name read through here.
+inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+
+// Each family below -- 3x3 convolutions, stride-2 layers, the post pass -- is a PLAN and a LAUNCH.  The plan is a pure host function of the
+// params struct, the epilogue, the shortcut flag and, where it matters, the batch size; it returns a plain stack value that names the kernel
+// form and what the form fixes.  The launch executes it and chooses no form; what depends on the batch inside a form (tile geometry,
+// persistence, grid shape) stays in that form's launcher.  Whoever asks what a launch will do reads the plan, never a copy of its rule.
+
 // launches (all stream-ordered, no sync)
-hipError_t launch_conv3x3(const ConvParams& p, int epi, bool shortcut, int n, hipStream_t s);
-bool conv_uses_ws(const ConvParams& p, int epi, bool shortcut, int n);
-bool conv_uses_ksplit(const ConvParams& p, bool shortcut);         // true: 4-way K split form (static rule: layer shape only)
-// The static shape rule of the Winograd forms, stated once: the commit (gsa_api.cpp) packs U by it, conv_uses_wino / conv_uses_wino43
-// select the kernel by it plus the clauses only a launch knows.  F(2x2,3x3): fp32 mode, outputs >= 64 px, or >= 32 px with >= 64 output
+// The kernel form of a 3x3 convolution, in the order the rule tries them.  Static: layer shape, arithmetic mode and switches, never the batch.
+enum class ConvForm { Wino43, WinoDma, WinoTwoTiles, WinoLean, Wino, KSplit, Bf16Lean, Direct };
+ConvForm conv3x3_form(const ConvParams& p, int epi, bool shortcut);
+hipError_t launch_conv3x3(const ConvParams& p, int epi, bool shortcut, int n, hipStream_t s);   // executes conv3x3_form(p, epi, shortcut)
+inline bool conv_form_wino(ConvForm f) { return f <= ConvForm::Wino; }      // a Winograd form: p.wino is the panel the kernel reads
+// products per output and (input, output) channel pair the form executes: F(4x4,3x3) 36 per 16 outputs, F(2x2,3x3) 16 per 4, direct 9
+inline double conv_form_products(ConvForm f) { return f == ConvForm::Wino43 ? 2.25 : conv_form_wino(f) ? 4 : 9; }
+// The static shape rule of the Winograd forms, stated once: the commit (gsa_api.cpp) packs U by it, conv3x3_form selects the kernel by it
+// plus the clauses only a launch knows.  F(2x2,3x3): fp32 mode, outputs >= 64 px, or >= 32 px with >= 64 output
 // channels, or >= 16 px with >= 256 (fewer tiles leave the chip idle: the direct small-tile kernels are faster there).  F(4x4,3x3): such
 // a layer with >= 64 input channels and >= 32 px.  The oracle's copy (oracle/c/gsa_oracle.c use_wino, use_wino43) stays separate on purpose.
 inline bool wino_shape(int H, int Cout, int bf16) { return !bf16 && (H >= 64 || (H >= 32 && Cout >= 64) || (H >= 16 && Cout >= 256)); }
 inline bool wino43_shape(int H, int Cin) { return Cin >= 64 && H >= 32; }
-bool conv_uses_wino43(const ConvParams& p, int epi, bool shortcut); // true: Winograd F(4x4,3x3) form (static rule: layer shape only; p.wino then holds the 36-frequency panel)
-bool wino43_enabled();                                              // GSA_WINO43 != 0
-bool conv_uses_wino(const ConvParams& p, int epi, bool shortcut);   // true: Winograd form (static rule: layer shape only)   // true: wave-specialised kernel, no partial rows
+bool wino43_enabled();                                              // GSA_WINO43 != 0 (experiments build)
 // gsa_wino_lean.hip (round 5): the Winograd layers with one 16-channel input block and one 16-channel output group in a leaner
 // instruction stream -- speed only, the same arithmetic and bits as conv3x3_wino (GSA_WINO_LEAN=0 keeps conv3x3_wino)
 bool wino_lean_applies(const ConvParams& p, int epi);
@@ -111,9 +127,25 @@ hipError_t launch_bf16_lean(const ConvParams& p, int epi, int n, hipStream_t s);
 // gsa_sub_lean.hip (round 5): subpixel_res<..., WINO> (fp32) in a leaner instruction stream -- speed only, same bits (GSA_SUB_LEAN=0: subpixel_res)
 bool subpixel_lean_applies(const ConvParams& p, int nt, int epi, bool sc, int kb, bool wst);
 hipError_t launch_subpixel_lean(const ConvParams& q, int nt, int epi, bool sc, int kb, bool wst, dim3 grid, hipStream_t s);
-hipError_t launch_subpixel(const ConvParams& p, int epi, bool shortcut, int n, hipStream_t s);   // deconv4x4s2 / sub-pixel up+conv
-bool subpixel_uses_wino(const ConvParams& p);                      // true: Winograd F(2x2,2x2) form (static rule: fp32 mode): 9 products per 2x2 class outputs instead of 163x3
-hipError_t launch_post(const PostParams& p, int n, hipStream_t s);
+// The plan of a stride-2 layer (deconv4x4s2 / sub-pixel up+conv): output channels per workgroup, the path, and what the path fixes
+enum class SubPath { Resident, Streamed, Plain };
+struct SubpixelPlan {
+    int ct;             // channel tile: 16, 32 or 64 output channels per workgroup
+    SubPath path;
+    bool wino;          // subpixel_uses_wino
+    int kb;             // Resident: channel blocks per item (1 or 2); Streamed: 1
+    size_t lds;         // Resident, Streamed: bytes of dynamic LDS (Plain: its launcher computes them)
+    int wgs_per_group;  // Streamed: workgroups per channel group
+};
+SubpixelPlan subpixel_plan(const ConvParams& p, bool shortcut, int n);
+hipError_t launch_subpixel(const ConvParams& p, int epi, bool shortcut, int n, hipStream_t s);   // executes subpixel_plan(p, shortcut, n)
+bool subpixel_uses_wino(const ConvParams& p);                      // true: Winograd F(2x2,2x2) form (static rule: fp32 mode): 9 products per 2x2 class outputs instead of 16
+// The plan of the post pass: the kernel, rows per thread, row groups per thread (post_rows_kernel<4>), workgroups per sample, and the
+// statistic partial rows per sample they write.  (The small planes of post_fuses_finalize go through launch_post_fin instead.)
+enum class PostKind { Dma, Packed, Rows, OneRow };
+struct PostPlan { PostKind kind; int rpt, row_groups, blocks, rows_used; };
+PostPlan post_plan(const PostParams& p);
+hipError_t launch_post(const PostParams& p, int n, hipStream_t s);      // executes post_plan(p)
 // gsa_post_lean.hip (round 5): post_rows_kernel<4> in packed fp32 arithmetic (same bits).  GSA_POST_PK: 0 = off, 1 = packed (default), 2 = + non-temporal stores
 int post_pk_mode();
 bool post_dma_applies(const PostParams& p);      // GSA_POST_DMA: the LDS-DMA ring form (16 / 32 channels, fp32, blurred)
@@ -155,7 +187,7 @@ hipError_t launch_final_conv(const float* src0, int C0, const float* src1, int C
 // geometry the launchers pick (weights are packed per 16 output channels, so it is free to vary)
 int conv_stat_rows(int H, int W, int Cout, int n);   // statistic partial rows per sample written by conv3x3 EPI_SYNTH
 int post_prow(int H, int W, int C);                  // ... written by the post kernel (upper bound: the one-row form)
-int post_rows_used(const PostParams& p);             // ... by the form launch_post picks for p
+int post_rows_used(const PostParams& p);             // ... by post_plan(p)
 hipError_t launch_fill_normal(float* out, int per_sample, int n, unsigned long long first_index, unsigned plane,
                               unsigned long long seed, hipStream_t s);
 hipError_t launch_seg_eval(const float* logits, const int8_t* labels, int n, int classes, int H, int W,

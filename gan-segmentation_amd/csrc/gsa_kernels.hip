@@ -1720,7 +1720,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_dma(ConvParams p) {
 // channels), the transformed patches the B operand (N = the 16 tiles of a 16x16 output region), K = input channels -- 72 MFMAs
 // per 8-channel block and 256 output pixels where conv3x3_wino issues 128.  Canonical arithmetic: oracle/c/gsa_oracle.c
 // conv3x3_wino43 (transform op order with its fmaf forms; U = G g G^T in double on the host, rounded once; each M_f one k-ordered
-// fmaf chain = the MFMA; K order of these layers: 8-channel blocks): reproduced BIT FOR BIT.  Static rule: conv_uses_wino43.
+// fmaf chain = the MFMA; K order of these layers: 8-channel blocks): reproduced BIT FOR BIT.  Static rule: ConvForm::Wino43 (conv3x3_form).
 // OPT-IN (GSA_WINO43=1): measured 15-20 % slower than conv3x3_wino on MI355X -- DESIGN.md section 4 "Round 4" has the five forms
 // this kernel went through, the stamps and the reasons; the body below is the last and fastest of them.
 //
@@ -3744,7 +3744,8 @@ __global__ __launch_bounds__(256) void fill_normal_kernel(float* out, int per_sa
 }
 
 // ========================================================================================
-// host-side launchers
+// host-side plans and launchers: per family one plan (conv3x3_form, subpixel_plan, post_plan: the only place that decides the kernel form,
+// pure, runs without a GPU) and the launchers that execute it -- see gsa_kernels.h.  Every rule clause is written once.
 
 // ---- launch helper (gsa_kernels.h) -----------------------------------------------------------------------------------------
 namespace {
@@ -3816,7 +3817,7 @@ std::string kernel_name(const void* kern) {
 // finalize_kernel always finds at most kDirectRows rows per sample: one block per channel group, every row load in flight at
 // once, no accumulator round trip and no ticket (it took 9-18 us per launch behind the 1024-row producers, ~3 us now)
 static bool few_rows() {
-    static const bool enabled = !(getenv("GSA_FEWROWS") && atoi(getenv("GSA_FEWROWS")) == 0);
+    static const bool enabled = env_int("GSA_FEWROWS", 1) != 0;
     return enabled;
 }
 
@@ -3859,7 +3860,7 @@ static hipError_t launch_conv_t(const ConvParams& p, int n, hipStream_t s) {
     constexpr int NBUF = (Q <= 2 && !SC && (TH == 16 || GSA_DB_SMALL)) ? 2 : 1;   // must match the kernel's DB
     // resident weights: one channel group and a whole panel of at most 40 KB (see the kernel)
     const int nblk_all = (p.C0 + p.C1) / 16;
-    static const bool wres_enabled = !(getenv("GSA_WRES") && atoi(getenv("GSA_WRES")) == 0);
+    static const bool wres_enabled = env_int("GSA_WRES", 1) != 0;
     const bool wres = wres_enabled && NBUF == 2 && p.Cout == COUT_T && (size_t)nblk_all * Q * 9 * TS * sizeof(float) <= 40 * 1024;
     if (NBUF == 1 && p.C0 > 512 && p.aff0) return hipErrorInvalidValue;   // AdaIN table registers sized for <= 512 channels
     const int wslots = wres ? nblk_all * Q * 9 * TS : NBUF * Q * 9 * TS;
@@ -3880,36 +3881,31 @@ static hipError_t launch_conv_t(const ConvParams& p, int n, hipStream_t s) {
     // prologue); long tiles pipeline inside the tile already and run ~8 % faster one tile per workgroup
     const bool persistent = (p.C0 + p.C1) <= 32 && q.total_tiles > num_cus * wgs_per_cu;
     const int grid = persistent ? num_cus * wgs_per_cu : q.total_tiles;
-    static const bool direct_enabled = !(getenv("GSA_STATS_DIRECT") && atoi(getenv("GSA_STATS_DIRECT")) == 0);
+    static const bool direct_enabled = env_int("GSA_STATS_DIRECT", 1) != 0;
     q.stats_direct = (direct_enabled && EPI == EPI_SYNTH && NBUF == 2 && persistent && p.partials != nullptr) ? 1 : 0;
     if (q.stats_direct) q.prow = kDirectRows;      // the rows are all zero between layers (finalize_kernel clears what it read)
     if (p.stat_rows_host) *p.stat_rows_host = q.prow;
     return launch<kern>(p.device, dim3(grid), dim3(64 * WM * WN), lds, s, q);
 }
 
-template <int TH, int TW, int WM, int WN, int NT, bool BF>
-static hipError_t launch_conv_b(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
-    if (sc) {
-        if (epi != EPI_DEC) return hipErrorInvalidValue;
-        return launch_conv_t<TH, TW, WM, WN, NT, EPI_DEC, true, BF>(p, n, s);
-    }
-    switch (epi) {
-        case EPI_RAW: return launch_conv_t<TH, TW, WM, WN, NT, EPI_RAW, false, BF>(p, n, s);
-        case EPI_SYNTH: return launch_conv_t<TH, TW, WM, WN, NT, EPI_SYNTH, false, BF>(p, n, s);
-        case EPI_DEC: return launch_conv_t<TH, TW, WM, WN, NT, EPI_DEC, false, BF>(p, n, s);
-    }
-    return hipErrorInvalidValue;
-}
-
+// the direct form at one geometry: arithmetic mode, epilogue and shortcut select the instantiation
 template <int TH, int TW, int WM, int WN, int NT>
-static hipError_t launch_conv_e(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
-    return p.bf16 ? launch_conv_b<TH, TW, WM, WN, NT, true>(p, epi, sc, n, s)
-                  : launch_conv_b<TH, TW, WM, WN, NT, false>(p, epi, sc, n, s);
+static hipError_t launch_conv_g(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
+    if (sc && epi != EPI_DEC) return hipErrorInvalidValue;
+#define GSA_EPI(BF) \
+    if (sc) return launch_conv_t<TH, TW, WM, WN, NT, EPI_DEC, true, BF>(p, n, s); \
+    if (epi == EPI_RAW) return launch_conv_t<TH, TW, WM, WN, NT, EPI_RAW, false, BF>(p, n, s); \
+    if (epi == EPI_SYNTH) return launch_conv_t<TH, TW, WM, WN, NT, EPI_SYNTH, false, BF>(p, n, s); \
+    if (epi == EPI_DEC) return launch_conv_t<TH, TW, WM, WN, NT, EPI_DEC, false, BF>(p, n, s); \
+    return hipErrorInvalidValue;
+    if (p.bf16) { GSA_EPI(true) }
+    GSA_EPI(false)
+#undef GSA_EPI
 }
 
 // ---- 4-way K split (static rule: the same one the oracle applies) -------------------------------------------------------
-bool conv_uses_ksplit(const ConvParams& p, bool sc) {
-    static const bool enabled = !(getenv("GSA_KSPLIT") && atoi(getenv("GSA_KSPLIT")) == 0);
+static bool ksplit_rule(const ConvParams& p, bool sc) {
+    static const bool enabled = env_int("GSA_KSPLIT", 1) != 0;
     return enabled && !sc && p.src1 == nullptr && p.C1 == 0 && p.C0 >= 64 && p.C0 % 64 == 0 && (p.H <= 8 || (p.H <= 32 && p.Cout <= 32)) && p.H == p.W && p.Cout % 16 == 0;
 }
 
@@ -3930,7 +3926,7 @@ static hipError_t launch_ksplit_t(const ConvParams& p, int n, hipStream_t s) {
 
 // waves per workgroup of the 8x8 form: 8 (patch split) unless GSA_KSPLIT_PS=1 (speed only, same bits)
 static int ksplit_ps() {
-    static const int forced = getenv("GSA_KSPLIT_PS") ? atoi(getenv("GSA_KSPLIT_PS")) : 2;
+    static const int forced = env_int("GSA_KSPLIT_PS", 2);
     return forced == 1 ? 1 : 2;
 }
 
@@ -3950,8 +3946,8 @@ static hipError_t launch_ksplit(const ConvParams& p, int epi, int n, hipStream_t
 // The rule is static (layer shape and arithmetic mode only, never the batch size): it is part of the canonical
 // arithmetic and the oracle applies the same one (oracle/c/gsa_oracle.c use_wino).  Its shape clause is wino_shape (gsa_kernels.h),
 // which the commit packs U by: a layer that passes it always has p.wino.
-bool conv_uses_wino(const ConvParams& p, int epi, bool sc) {
-    static const bool enabled = !(getenv("GSA_WINO") && atoi(getenv("GSA_WINO")) == 0);
+static bool wino_rule(const ConvParams& p, int epi, bool sc) {
+    static const bool enabled = env_int("GSA_WINO", 1) != 0;
     return enabled && p.wino != nullptr && !sc && !p.up && p.src1 == nullptr && p.C1 == 0 && epi != EPI_RAW &&
            wino_shape(p.H, p.Cout, p.bf16) && p.H == p.W && p.H % 16 == 0 && p.Cout % 16 == 0 && p.C0 % 16 == 0;
 }
@@ -3960,7 +3956,7 @@ bool conv_uses_wino(const ConvParams& p, int epi, bool sc) {
 // the staging shared by 32 output channels) measured SLOWER than two NT = 1 workgroups per CU (g.512.conv_2: 0.35 vs 0.30 ms):
 // a lone wave per SIMD does not hide its own LDS / MFMA latencies.  Kept for A/B runs (GSA_WINO_NT=2); speed only, same bits.
 static int wino_nt(const ConvParams& p) {
-    static const int forced = getenv("GSA_WINO_NT") ? atoi(getenv("GSA_WINO_NT")) : 1;
+    static const int forced = env_int("GSA_WINO_NT", 1);
     return (forced >= 2 && p.Cout % 32 == 0) ? 2 : 1;
 }
 
@@ -3990,17 +3986,17 @@ static hipError_t launch_wino_t(const ConvParams& p, int n, hipStream_t s) {
     // its two-item prefetch full across tiles: g.256.conv_2 0.292 -> 0.249 ms, d.cvt_6 0.150 -> 0.133, g.128.conv_2 0.247 -> 0.233,
     // g.64 / g.32.conv_2 0.233 / 0.229 -> 0.224 / 0.225 (same box).  The groups of a tile range still meet in one XCD's L2: workgroup
     // (x, g) has the linear index x + g * gx and gx is a multiple of 8.  GSA_WINO_PERS=<max input channels> restores a limit.
-    static const int pers_c = getenv("GSA_WINO_PERS") ? atoi(getenv("GSA_WINO_PERS")) : 1 << 30;
+    static const int pers_c = env_int("GSA_WINO_PERS", 1 << 30);
     const bool persistent = p.C0 <= pers_c && q.total_tiles > slots;
     const int gx = persistent ? slots : q.total_tiles;
-    static const bool direct_enabled = !(getenv("GSA_STATS_DIRECT") && atoi(getenv("GSA_STATS_DIRECT")) == 0);
+    static const bool direct_enabled = env_int("GSA_STATS_DIRECT", 1) != 0;
     // direct statistics: always for persistent workgroups; for one-tile workgroups when the layer would otherwise write
     // more than kDirectRows rows (few_rows).  The rows are all zero between layers (finalize_kernel clears what it read).
     q.stats_direct = (direct_enabled && EPI == EPI_SYNTH && p.partials != nullptr && (persistent || (few_rows() && q.prow > kDirectRows))) ? 1 : 0;
     if (q.stats_direct) q.prow = kDirectRows;
     if (p.stat_rows_host) *p.stat_rows_host = q.prow;
     // groups of a tile side by side on one XCD when the layer's whole U (16 * Cin * Cout floats) fits comfortably in a 4 MB L2
-    static const bool gm_enabled = !(getenv("GSA_WINO_GM") && atoi(getenv("GSA_WINO_GM")) == 0);
+    static const bool gm_enabled = env_int("GSA_WINO_GM", 1) != 0;
     q.group_minor = (gm_enabled && !persistent && q.groups > 1 && q.total_tiles % 8 == 0 &&
                      (size_t)16 * p.C0 * p.Cout * sizeof(float) <= (size_t)2 << 20) ? 1 : 0;
     const dim3 grid = q.group_minor ? dim3(q.total_tiles * q.groups) : dim3(gx, q.groups);
@@ -4014,11 +4010,8 @@ static hipError_t launch_wino_t(const ConvParams& p, int n, hipStream_t s) {
 // product keeps F(2x2,3x3).
 #if GSA_EXPERIMENTS
 bool wino43_enabled() {
-    static const bool enabled = getenv("GSA_WINO43") && atoi(getenv("GSA_WINO43")) != 0;
+    static const bool enabled = env_int("GSA_WINO43", 0) != 0;
     return enabled;
-}
-bool conv_uses_wino43(const ConvParams& p, int epi, bool sc) {
-    return wino43_enabled() && conv_uses_wino(p, epi, sc) && wino43_shape(p.H, p.C0) && p.resid == nullptr;
 }
 
 template <int EPI>
@@ -4051,12 +4044,11 @@ static hipError_t launch_wino43(const ConvParams& p, int epi, int n, hipStream_t
 
 #else
 bool wino43_enabled() { return false; }
-bool conv_uses_wino43(const ConvParams&, int, bool) { return false; }
 #endif
 
 // staging form of the Winograd kernel: 16-byte chunks from 64 input channels on, whole pixels below (measured; speed only)
 static bool wino_chunk(const ConvParams& p) {
-    static const int forced = getenv("GSA_WINO_CHUNK") ? atoi(getenv("GSA_WINO_CHUNK")) : -1;
+    static const int forced = env_int("GSA_WINO_CHUNK", -1);
     return forced >= 0 ? forced != 0 : p.C0 >= 64;
 }
 
@@ -4066,7 +4058,7 @@ static bool wino_chunk(const ConvParams& p) {
 // SLOWER with it (g.32...g.256.conv_2 0.234/0.237/0.248/0.294 -> 0.256/0.257/0.253/0.298: their eight waves then wait on one
 // barrier for a 32 KB weight block per item) and keep one group per workgroup.  GSA_WINO_GW=1 / 2 force it (speed only, same bits).
 static int wino_gw(const ConvParams& p) {
-    static const int forced = getenv("GSA_WINO_GW") ? atoi(getenv("GSA_WINO_GW")) : 0;
+    static const int forced = env_int("GSA_WINO_GW", 0);
     if (wino_nt(p) != 1 || p.Cout % 32 != 0 || forced == 1) return 1;
     return (forced >= 2 || p.C0 <= 32) ? 2 : 1;
 }
@@ -4076,7 +4068,7 @@ static int wino_gw(const ConvParams& p) {
 // arithmetic as conv3x3_wino, same bits -- and measured 8-10 % SLOWER (g.64.conv_2 0.250 vs 0.227 ms: ~260 cycles per DMA instruction
 // with eight waves per CU, and every wave waits at the barrier for the slowest wave's DMA): opt-in, GSA_WINO_DMA=1, for A/B runs.
 static bool wino_dma(const ConvParams& p, int epi) {
-    static const bool enabled = getenv("GSA_WINO_DMA") && atoi(getenv("GSA_WINO_DMA")) != 0;
+    static const bool enabled = env_int("GSA_WINO_DMA", 0) != 0;
     return enabled && p.C0 >= 64 && p.zeros != nullptr && p.resid == nullptr && (epi == EPI_SYNTH ? p.partials != nullptr : true);
 }
 
@@ -4108,7 +4100,7 @@ static hipError_t launch_wino_dma(const ConvParams& p, int epi, int n, hipStream
 // two 16x16 tiles per 8-wave workgroup (conv3x3_wino<..., TW = 2>): the layers with ONE output-channel group and a resident panel
 // (16 output channels from <= 32 inputs: g.1024.conv_2, d.cvt_8, d.main_7.b), whole-pixel staging.  GSA_WINO_TW=2 selects it (speed only).
 static int wino_tw(const ConvParams& p) {
-    static const int forced = getenv("GSA_WINO_TW") ? atoi(getenv("GSA_WINO_TW")) : 1;
+    static const int forced = env_int("GSA_WINO_TW", 1);
     return (forced == 2 && p.Cout == 16 && p.C0 <= 32 && p.W % 32 == 0 && wino_nt(p) == 1 && !wino_chunk(p)) ? 2 : 1;
 }
 
@@ -4117,28 +4109,15 @@ static bool wino_dma(const ConvParams&, int) { return false; }
 static int wino_tw(const ConvParams&) { return 1; }
 #endif
 
-// The kernel a Winograd layer (conv_uses_wino) runs.  An explicitly selected experiment wins over the lean kernels.
-enum class WinoForm { F43, Dma, TwoTiles, Lean, General };
-static WinoForm wino_form(const ConvParams& p, int epi, bool sc) {
-    if (conv_uses_wino43(p, epi, sc)) return WinoForm::F43;
-    if (wino_dma(p, epi) && wino_nt(p) == 1) return WinoForm::Dma;
-    if (wino_tw(p) == 2) return WinoForm::TwoTiles;
-    if (wino_lean_applies(p, epi)) return WinoForm::Lean;
-    return WinoForm::General;
-}
-
-static hipError_t launch_wino(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
-    switch (wino_form(p, epi, sc)) {
 #if GSA_EXPERIMENTS
-        case WinoForm::F43: return launch_wino43(p, epi, n, s);
-        case WinoForm::Dma: return launch_wino_dma(p, epi, n, s);
-        case WinoForm::TwoTiles:
-            if (epi == EPI_SYNTH) return p.aff0 ? launch_wino_t<EPI_SYNTH, 1, false, true, 1, 2>(p, n, s) : launch_wino_t<EPI_SYNTH, 1, false, false, 1, 2>(p, n, s);
-            return p.aff0 ? launch_wino_t<EPI_DEC, 1, false, true, 1, 2>(p, n, s) : launch_wino_t<EPI_DEC, 1, false, false, 1, 2>(p, n, s);
+static hipError_t launch_wino_two_tiles(const ConvParams& p, int epi, int n, hipStream_t s) {
+    if (epi == EPI_SYNTH) return p.aff0 ? launch_wino_t<EPI_SYNTH, 1, false, true, 1, 2>(p, n, s) : launch_wino_t<EPI_SYNTH, 1, false, false, 1, 2>(p, n, s);
+    return p.aff0 ? launch_wino_t<EPI_DEC, 1, false, true, 1, 2>(p, n, s) : launch_wino_t<EPI_DEC, 1, false, false, 1, 2>(p, n, s);
+}
 #endif
-        case WinoForm::Lean: return launch_wino_lean(p, epi, n, s);
-        default: break;
-    }
+
+// the general F(2x2,3x3) kernel: groups per workgroup and staging are speed-only shapes of the one form
+static hipError_t launch_wino(const ConvParams& p, int epi, int n, hipStream_t s) {
     const int nt = wino_nt(p);
     const int gw = wino_gw(p);
     const bool ch = wino_chunk(p);
@@ -4155,20 +4134,10 @@ static hipError_t launch_wino(const ConvParams& p, int epi, bool sc, int n, hipS
 #undef GSA_W
 }
 
-// true: launch_conv3x3(p, epi, sc) with p.rgb_* set also writes toRGB's uint8 image -- i.e. the call reaches the lean 16 -> 16 kernel (an
-// experiment switch that takes the layer elsewhere, or the F(4x4,3x3) form, rules it out: they know nothing of rgb_img)
-bool conv_fuses_torgb(const ConvParams& p, int epi, bool sc, int nc) {
-    return conv_uses_wino(p, epi, sc) && wino_form(p, epi, sc) == WinoForm::Lean && wino_lean_fuses_torgb(p, epi, nc);
-}
-
-hipError_t launch_conv3x3(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
-    if (p.H != p.W || (p.H & (p.H - 1)) || p.H < 4 || p.Cout % 16 || p.C0 % 16 || p.C1 % 16) return hipErrorInvalidValue;
-    if (conv_uses_wino(p, epi, sc)) return launch_wino(p, epi, sc, n, s);
-    if (conv_uses_ksplit(p, sc)) return launch_ksplit(p, epi, n, s);
-    if (bf16_lean_applies(p, epi, sc)) return launch_bf16_lean(p, epi, n, s);
+static hipError_t launch_direct(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
     const ConvGeom c = pick_geom(p.H, p.W, p.Cout, n);
 #define GSA_GEOM(TH, WM, WN, NT) \
-    if (c.th == TH && c.wm == WM && c.wn == WN && c.nt == NT) return launch_conv_e<TH, TH, WM, WN, NT>(p, epi, sc, n, s);
+    if (c.th == TH && c.wm == WM && c.wn == WN && c.nt == NT) return launch_conv_g<TH, TH, WM, WN, NT>(p, epi, sc, n, s);
     GSA_GEOM(4, 1, 4, 1) GSA_GEOM(4, 1, 2, 1) GSA_GEOM(4, 1, 1, 1)
     GSA_GEOM(8, 4, 1, 4) GSA_GEOM(8, 4, 1, 2) GSA_GEOM(8, 4, 1, 1)
     GSA_GEOM(16, 4, 1, 4) GSA_GEOM(16, 4, 1, 2) GSA_GEOM(16, 4, 1, 1)
@@ -4176,230 +4145,225 @@ hipError_t launch_conv3x3(const ConvParams& p, int epi, bool sc, int n, hipStrea
     return hipErrorInvalidValue;
 }
 
+// ---- the plan of a 3x3 convolution ------------------------------------------------------------------------------------------
+// Winograd, then K split, then the bf16 lean kernel, then the direct kernel; inside Winograd an explicitly selected experiment wins
+// over the lean kernels.  F(4x4,3x3) (oracle/c/gsa_oracle.c use_wino43): a Winograd layer without a residual epilogue, with at least
+// 64 input channels (the streamed-weight layers) and an output of at least 32 px.
+ConvForm conv3x3_form(const ConvParams& p, int epi, bool sc) {
+    if (wino_rule(p, epi, sc)) {
+        if (wino43_enabled() && wino43_shape(p.H, p.C0) && p.resid == nullptr) return ConvForm::Wino43;
+        if (wino_dma(p, epi) && wino_nt(p) == 1) return ConvForm::WinoDma;
+        if (wino_tw(p) == 2) return ConvForm::WinoTwoTiles;
+        return wino_lean_applies(p, epi) ? ConvForm::WinoLean : ConvForm::Wino;
+    }
+    if (ksplit_rule(p, sc)) return ConvForm::KSplit;
+    return bf16_lean_applies(p, epi, sc) ? ConvForm::Bf16Lean : ConvForm::Direct;
+}
+
+hipError_t launch_conv3x3(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
+    if (p.H != p.W || (p.H & (p.H - 1)) || p.H < 4 || p.Cout % 16 || p.C0 % 16 || p.C1 % 16) return hipErrorInvalidValue;
+    switch (conv3x3_form(p, epi, sc)) {
+#if GSA_EXPERIMENTS
+        case ConvForm::Wino43: return launch_wino43(p, epi, n, s);
+        case ConvForm::WinoDma: return launch_wino_dma(p, epi, n, s);
+        case ConvForm::WinoTwoTiles: return launch_wino_two_tiles(p, epi, n, s);
+#endif
+        case ConvForm::WinoLean: return launch_wino_lean(p, epi, n, s);
+        case ConvForm::Wino: return launch_wino(p, epi, n, s);
+        case ConvForm::KSplit: return launch_ksplit(p, epi, n, s);
+        case ConvForm::Bf16Lean: return launch_bf16_lean(p, epi, n, s);
+        case ConvForm::Direct: return launch_direct(p, epi, sc, n, s);
+        default: return hipErrorInvalidValue;      // a form only the experiments build has a kernel for (its switches are off here)
+    }
+}
+
+// whole-plane K-split tiles (4 and 8 px) finalize in the kernel when the caller supplies the finalize operands (GSA_FUSEFIN=0: never)
+static bool fuse_finalize() {
+    static const bool enabled = env_int("GSA_FUSEFIN", 1) != 0;
+    return enabled;
+}
+bool conv_fuses_finalize(const ConvParams& p, int epi, bool sc) {
+    return fuse_finalize() && epi == EPI_SYNTH && p.H <= 8 && conv3x3_form(p, epi, sc) == ConvForm::KSplit;
+}
+
+// true: launch_conv3x3(p, epi, sc) with p.rgb_* set also writes toRGB's uint8 image -- the plan is the lean kernel, whose 16 -> 16
+// instantiation knows rgb_img (no other form does, so an experiment switch that takes the layer elsewhere rules it out by itself)
+bool conv_fuses_torgb(const ConvParams& p, int epi, bool sc, int nc) {
+    return conv3x3_form(p, epi, sc) == ConvForm::WinoLean && wino_lean_fuses_torgb(p, epi, nc);
+}
+
+// ---- stride-2 layers ------------------------------------------------------------------------------------------------------------
 // Winograd F(2x2,2x2) form of the stride-2 layers: every such layer in fp32 mode (the static rule of the canonical arithmetic,
 // oracle/c/gsa_oracle.c use_wino22).  GSA_WINO22=0 selects the direct 4-tap kernels -- a different arithmetic, timing only.
-static bool sub_wino(const ConvParams& p) {
-    static const bool enabled = !(getenv("GSA_WINO22") && atoi(getenv("GSA_WINO22")) == 0);
+bool subpixel_uses_wino(const ConvParams& p) {
+    static const bool enabled = env_int("GSA_WINO22", 1) != 0;
     return enabled && !p.bf16;
 }
-bool subpixel_uses_wino(const ConvParams& p) { return sub_wino(p); }
-static int sub_rs(const ConvParams& p) { return p.bf16 ? 10 * 8 + 4 : 10 * 16 + (sub_wino(p) ? 4 : 8); }      // LDS row stride in 4-byte slots
 
-template <int NT, int EPI, bool SC, bool BF, bool WINO = false>
-static hipError_t launch_subpixel_t(const ConvParams& p, int n, hipStream_t s) {
-    constexpr int COUT_T = 16 * NT, TS = BF ? 128 : 256;
-    const size_t lds = sizeof(float) * (10 * (10 * (BF ? 8 : 16) + (BF || WINO ? 4 : 8)) + NT * 16 * TS + (SC ? NT * TS : 0)) + (p.aff0 ? sizeof(float4) * p.C0 : 0);
-    ConvParams q = p;
-    q.tiles_x = p.W / 16;
-    const dim3 grid((p.H / 16) * (p.W / 16), p.Cout / COUT_T, n);
-    return launch<subpixel_mfma<NT, EPI, SC, BF, WINO>>(p.device, grid, dim3(256), lds, s, q);
-}
-
-// channel blocks per item of subpixel_res: 2 when the block count is even and the doubled activation buffers still fit
-static int subpixel_res_kb(const ConvParams& p);
-
-// persistent form with the LDS-resident weight panel (subpixel_res): one 512-thread workgroup per CU
-template <int NT, int EPI, bool SC, bool BF, int KB, bool WINO>
-static hipError_t launch_subpixel_res_k(const ConvParams& p, int n, size_t lds, hipStream_t s) {
-    const int num_cus = device_cus(p.device);
-    ConvParams q = p;
-    q.tiles_x = p.W / 16;
-    q.tiles_y = p.H / 16;
-    q.groups = 1;
-    q.total_tiles = q.tiles_x * q.tiles_y * n;
-    const int grid = std::min(num_cus, (q.total_tiles + 1) / 2);
-    if (WINO && !BF && subpixel_lean_applies(q, NT, EPI, SC, KB, false)) return launch_subpixel_lean(q, NT, EPI, SC, KB, false, dim3(grid), s);
-    return launch<subpixel_res<NT, EPI, SC, BF, KB, false, WINO>>(p.device, dim3(grid), dim3(512), lds, s, q);
-}
-
-// streamed-weights form: grid (workgroups per channel group, channel groups)
-template <int NT, int EPI, bool SC, bool BF, bool WINO = false>
-static hipError_t launch_subpixel_wst_t(const ConvParams& p, int n, size_t lds, int wgs_per_g, hipStream_t s) {
-    ConvParams q = p;
-    q.tiles_x = p.W / 16;
-    q.tiles_y = p.H / 16;
-    q.groups = p.Cout / (16 * NT);
-    q.total_tiles = q.tiles_x * q.tiles_y * n;       // per channel group
-    if (WINO && !BF && subpixel_lean_applies(q, NT, EPI, SC, 1, true)) return launch_subpixel_lean(q, NT, EPI, SC, 1, true, dim3(wgs_per_g, q.groups), s);
-    return launch<subpixel_res<NT, EPI, SC, BF, 1, true, WINO>>(p.device, dim3(wgs_per_g, q.groups), dim3(512), lds, s, q);
-}
-
-// Streamed form: LDS bytes and workgroups per channel group, or 0 when it does not pay (fewer than 2 tiles per half)
-static size_t subpixel_wst_lds(const ConvParams& p, int ct, bool sc, int n, int* wgs_per_g) {
-    static const bool enabled = !(getenv("GSA_SUBWST") && atoi(getenv("GSA_SUBWST")) == 0);
-    const int num_cus = device_cus(p.device);
-    if (!enabled || p.Cout % ct) return 0;
-    const int ts = p.bf16 ? 128 : 256, rs = sub_rs(p);
-    const int nt = ct / 16, groups = p.Cout / ct;
-    const size_t lds = sizeof(float) * ((size_t)2 * nt * 16 * ts + (sc ? (size_t)2 * nt * ts : 0) + 4 * 10 * rs) + 64 * sizeof(float4);
+// The plan of a stride-2 layer.  Channel tile: the widest that still gives the chip >= 2 workgroups per CU (else the narrowest).  Then
+// the first path that applies:
+//   Resident  subpixel_res with the whole weight panel in LDS, one persistent 512-thread workgroup per CU: one channel group of 16 or 32
+//             channels, at least 4096 tiles; kb = channel blocks per item, 2 when the block count is even and the doubled activation
+//             buffers still fit beside the panel in 160 KB (the layer does not qualify when even kb = 1 does not fit)
+//   Streamed  subpixel_res with the weights streamed, grid (workgroups per channel group, channel groups): at least 2 tiles per half
+//   Plain     subpixel_mfma, one tile per workgroup
+SubpixelPlan subpixel_plan(const ConvParams& p, bool sc, int n) {
+    static const bool res_enabled = env_int("GSA_SUBRES", 1) != 0;
+    static const bool wst_enabled = env_int("GSA_SUBWST", 1) != 0;
+    SubpixelPlan plan{};
+    plan.wino = subpixel_uses_wino(p);
     const long tiles = (long)(p.H / 16) * (p.W / 16) * n;
-    const int wgs = std::max(1, num_cus / groups);
-    if (lds > 160 * 1024 || tiles < 4L * wgs) return 0;
-    *wgs_per_g = wgs;
-    return lds;
-}
-
-template <int NT, int EPI, bool SC, bool BF, bool WINO = false>
-static hipError_t launch_subpixel_res_t(const ConvParams& p, int n, size_t lds, hipStream_t s) {
-    return subpixel_res_kb(p) == 2 ? launch_subpixel_res_k<NT, EPI, SC, BF, 2, WINO>(p, n, lds, s)
-                                   : launch_subpixel_res_k<NT, EPI, SC, BF, 1, WINO>(p, n, lds, s);
-}
-
-// LDS bytes of subpixel_res for this layer, or 0 when the layer does not qualify (several channel groups, a
-// weight panel beyond ~100 KB, too few tiles to keep every CU busy)
-static size_t subpixel_res_lds(const ConvParams& p, int ct, bool sc, int n) {
-    static const bool enabled = !(getenv("GSA_SUBRES") && atoi(getenv("GSA_SUBRES")) == 0);
-    if (!enabled || ct != p.Cout || ct > 32) return 0;      // instantiated for 16 and 32 output channels
-    const int ts = p.bf16 ? 128 : 256, rs = sub_rs(p);
-    const int nblk = (p.C0 + p.C1) / 16, nt = ct / 16;
-    const size_t fixed = sizeof(float) * ((size_t)nblk * nt * 16 * ts + (sc ? (size_t)nblk * nt * ts : 0));
-    const long tiles = (long)(p.H / 16) * (p.W / 16) * n;
-    if (tiles < 4096) return 0;
-    const int kb_min_blocks = sub_wino(p) ? 2 : 4;      // Winograd form: 36 MFMAs per block instead of 64 -- a two-block tile is one item
-    for (int kb = (nblk % 2 == 0 && nblk >= kb_min_blocks) ? 2 : 1; kb >= 1; --kb) {     // two blocks per item pay off from 4 blocks on
-        const size_t lds = fixed + sizeof(float) * 4 * kb * 10 * rs + 64 * kb * sizeof(float4);
-        if (lds <= 160 * 1024) return lds;
+    plan.ct = 16;
+    for (int ct = plan.wino ? 32 : 64; ct > 16; ct /= 2)      // Winograd form: nine accumulator vectors per 16 channels -- at most 32 per workgroup
+        if (p.Cout % ct == 0 && tiles * (p.Cout / ct) >= 512) { plan.ct = ct; break; }
+    const int ts = p.bf16 ? 128 : 256, nt = plan.ct / 16;
+    const int rs = p.bf16 ? 10 * 8 + 4 : 10 * 16 + (plan.wino ? 4 : 8);      // LDS row stride in 4-byte slots
+    if (res_enabled && plan.ct == p.Cout && plan.ct <= 32 && tiles >= 4096) {      // instantiated for 16 and 32 output channels
+        const int nblk = (p.C0 + p.C1) / 16;
+        const size_t panel = sizeof(float) * ((size_t)nblk * nt * 16 * ts + (sc ? (size_t)nblk * nt * ts : 0));
+        const int kb_min_blocks = plan.wino ? 2 : 4;      // Winograd form: 36 MFMAs per block instead of 64 -- a two-block tile is one item
+        for (int kb = (nblk % 2 == 0 && nblk >= kb_min_blocks) ? 2 : 1; kb >= 1; --kb) {     // two blocks per item pay off from 4 blocks on
+            const size_t lds = panel + sizeof(float) * 4 * kb * 10 * rs + 64 * kb * sizeof(float4);
+            if (lds <= 160 * 1024) { plan.path = SubPath::Resident; plan.kb = kb; plan.lds = lds; return plan; }
+        }
     }
-    return 0;
+    if (wst_enabled && p.Cout % plan.ct == 0) {
+        const size_t lds = sizeof(float) * ((size_t)2 * nt * 16 * ts + (sc ? (size_t)2 * nt * ts : 0) + 4 * 10 * rs) + 64 * sizeof(float4);
+        const int wgs = std::max(1, device_cus(p.device) / (p.Cout / plan.ct));
+        if (lds <= 160 * 1024 && tiles >= 4L * wgs) { plan.path = SubPath::Streamed; plan.kb = 1; plan.lds = lds; plan.wgs_per_group = wgs; return plan; }
+    }
+    plan.path = SubPath::Plain;
+    return plan;
 }
 
-static int subpixel_res_kb(const ConvParams& p) {
-    const int ts = p.bf16 ? 128 : 256, rs = sub_rs(p);
-    const int nblk = (p.C0 + p.C1) / 16, nt = p.Cout / 16;
-    const bool sc = p.wsc != nullptr;
-    const size_t fixed = sizeof(float) * ((size_t)nblk * nt * 16 * ts + (sc ? (size_t)nblk * nt * ts : 0));
-    if (nblk % 2 || nblk < (sub_wino(p) ? 2 : 4)) return 1;
-    return fixed + sizeof(float) * 4 * 2 * 10 * rs + 128 * sizeof(float4) <= 160 * 1024 ? 2 : 1;
+// subpixel_res<KB, WST> at the grid and LDS size of the plan; the fp32 Winograd launches gsa_sub_lean.hip takes go to its kernels (same bits)
+template <int NT, int EPI, bool SC, bool BF, int KB, bool WST, bool WINO>
+static hipError_t launch_subpixel_res(const ConvParams& q, dim3 grid, size_t lds, hipStream_t s) {
+    if (WINO && !BF && subpixel_lean_applies(q, NT, EPI, SC, KB, WST)) return launch_subpixel_lean(q, NT, EPI, SC, KB, WST, grid, s);
+    return launch<subpixel_res<NT, EPI, SC, BF, KB, WST, WINO>>(q.device, grid, dim3(512), lds, s, q);
 }
 
-// widest channel tile that still gives the chip >= 2 workgroups per CU (else the narrowest)
-static int subpixel_cout_tile(int H, int W, int Cout, int n, bool wino) {
-    const long tiles = (long)(H / 16) * (W / 16) * n;
-    for (int ct = wino ? 32 : 64; ct >= 16; ct /= 2)      // Winograd form: nine accumulator vectors per 16 channels -- at most 32 per workgroup
-        if (Cout % ct == 0 && (tiles * (Cout / ct) >= 512 || ct == 16)) return ct;
-    return 16;
+// One enumeration of the stride-2 instantiations: the (NT, BF, WINO) rows of launch_subpixel_path x {DEC with shortcut, DEC, RAW}.  The Winograd
+// form exists in fp32 and up to 32 channels per workgroup, the resident panel up to 32 channels: 6 rows on the resident path, 8 on the other two.
+template <SubPath PATH, int NT, bool BF, bool WINO>
+constexpr bool kSubpixelRow = !(WINO && (BF || NT == 4)) && !(PATH == SubPath::Resident && NT == 4);
+
+template <SubPath PATH, int NT, int EPI, bool SC, bool BF, bool WINO>
+static hipError_t launch_subpixel_t(const ConvParams& p, const SubpixelPlan& plan, int n, hipStream_t s) {
+    ConvParams q = p;
+    q.tiles_x = p.W / 16;
+    if constexpr (PATH == SubPath::Plain) {      // subpixel_mfma, one tile per workgroup
+        constexpr int TS = BF ? 128 : 256;
+        const size_t lds = sizeof(float) * (10 * (10 * (BF ? 8 : 16) + (BF || WINO ? 4 : 8)) + NT * 16 * TS + (SC ? NT * TS : 0)) + (p.aff0 ? sizeof(float4) * p.C0 : 0);
+        const dim3 grid((p.H / 16) * (p.W / 16), p.Cout / (16 * NT), n);
+        return launch<subpixel_mfma<NT, EPI, SC, BF, WINO>>(p.device, grid, dim3(256), lds, s, q);
+    } else {
+        constexpr bool WST = PATH == SubPath::Streamed;
+        q.tiles_y = p.H / 16;
+        q.groups = WST ? p.Cout / (16 * NT) : 1;
+        q.total_tiles = q.tiles_x * q.tiles_y * n;       // per channel group
+        const dim3 grid = WST ? dim3(plan.wgs_per_group, q.groups) : dim3(std::min(device_cus(p.device), (q.total_tiles + 1) / 2));
+        if constexpr (!WST)
+            if (plan.kb == 2) return launch_subpixel_res<NT, EPI, SC, BF, 2, false, WINO>(q, grid, plan.lds, s);
+        return launch_subpixel_res<NT, EPI, SC, BF, 1, WST, WINO>(q, grid, plan.lds, s);
+    }
+}
+
+template <SubPath PATH, int NT, bool BF, bool WINO>
+static hipError_t launch_subpixel_row(const ConvParams& p, const SubpixelPlan& plan, int epi, bool sc, int n, hipStream_t s) {
+    if constexpr (kSubpixelRow<PATH, NT, BF, WINO>) {
+        if (sc) return launch_subpixel_t<PATH, NT, EPI_DEC, true, BF, WINO>(p, plan, n, s);
+        if (epi == EPI_DEC) return launch_subpixel_t<PATH, NT, EPI_DEC, false, BF, WINO>(p, plan, n, s);
+        if (epi == EPI_RAW) return launch_subpixel_t<PATH, NT, EPI_RAW, false, BF, WINO>(p, plan, n, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <SubPath PATH>
+static hipError_t launch_subpixel_path(const ConvParams& p, const SubpixelPlan& plan, int epi, bool sc, int n, hipStream_t s) {
+#define GSA_ROW(NT, BF, WN) \
+    if (plan.ct == 16 * NT && (p.bf16 != 0) == BF && plan.wino == WN) return launch_subpixel_row<PATH, NT, BF, WN>(p, plan, epi, sc, n, s);
+    GSA_ROW(1, false, false) GSA_ROW(2, false, false) GSA_ROW(4, false, false) GSA_ROW(1, true, false) GSA_ROW(2, true, false) GSA_ROW(4, true, false)
+    GSA_ROW(1, false, true) GSA_ROW(2, false, true)
+#undef GSA_ROW
+    return hipErrorInvalidValue;
 }
 
 // deconv 4x4 s2 p1, or nearest-x2 + conv3x3 with host-presummed weights (same kernel)
 hipError_t launch_subpixel(const ConvParams& p, int epi, bool sc, int n, hipStream_t s) {
     if (p.H != 2 * p.Hs || p.W != 2 * p.Ws || p.H % 16 || p.W % 16 || p.Cout % 16 || p.C0 % 16 || p.C1 % 16) return hipErrorInvalidValue;
     if (sc && epi != EPI_DEC) return hipErrorInvalidValue;
-    const bool wino = sub_wino(p);
-    const int ct = subpixel_cout_tile(p.H, p.W, p.Cout, n, wino);
-    if (const size_t rlds = subpixel_res_lds(p, ct, sc, n)) {
-#define GSA_SUBR(NT, BF, WN) \
-        if (ct == 16 * NT && (p.bf16 != 0) == BF && wino == WN) { \
-            if (sc) return launch_subpixel_res_t<NT, EPI_DEC, true, BF, WN>(p, n, rlds, s); \
-            if (epi == EPI_DEC) return launch_subpixel_res_t<NT, EPI_DEC, false, BF, WN>(p, n, rlds, s); \
-            if (epi == EPI_RAW) return launch_subpixel_res_t<NT, EPI_RAW, false, BF, WN>(p, n, rlds, s); \
-            return hipErrorInvalidValue; \
-        }
-        GSA_SUBR(1, false, false) GSA_SUBR(2, false, false) GSA_SUBR(1, true, false) GSA_SUBR(2, true, false)
-        GSA_SUBR(1, false, true) GSA_SUBR(2, false, true)
-#undef GSA_SUBR
+    const SubpixelPlan plan = subpixel_plan(p, sc, n);
+    switch (plan.path) {
+        case SubPath::Resident: return launch_subpixel_path<SubPath::Resident>(p, plan, epi, sc, n, s);
+        case SubPath::Streamed: return launch_subpixel_path<SubPath::Streamed>(p, plan, epi, sc, n, s);
+        case SubPath::Plain: return launch_subpixel_path<SubPath::Plain>(p, plan, epi, sc, n, s);
     }
-    int wgs_per_g = 0;
-    if (const size_t wlds = subpixel_wst_lds(p, ct, sc, n, &wgs_per_g)) {
-#define GSA_SUBW(NT, BF, WN) \
-        if (ct == 16 * NT && (p.bf16 != 0) == BF && wino == WN) { \
-            if (sc) return launch_subpixel_wst_t<NT, EPI_DEC, true, BF, WN>(p, n, wlds, wgs_per_g, s); \
-            if (epi == EPI_DEC) return launch_subpixel_wst_t<NT, EPI_DEC, false, BF, WN>(p, n, wlds, wgs_per_g, s); \
-            if (epi == EPI_RAW) return launch_subpixel_wst_t<NT, EPI_RAW, false, BF, WN>(p, n, wlds, wgs_per_g, s); \
-            return hipErrorInvalidValue; \
-        }
-        GSA_SUBW(1, false, false) GSA_SUBW(2, false, false) GSA_SUBW(4, false, false) GSA_SUBW(1, true, false) GSA_SUBW(2, true, false) GSA_SUBW(4, true, false)
-        GSA_SUBW(1, false, true) GSA_SUBW(2, false, true)
-#undef GSA_SUBW
-    }
-#define GSA_SUB(NT) \
-    if (ct == 16 * NT && wino && NT <= 2) { \
-        if (sc) return launch_subpixel_t<(NT <= 2 ? NT : 1), EPI_DEC, true, false, true>(p, n, s); \
-        if (epi == EPI_DEC) return launch_subpixel_t<(NT <= 2 ? NT : 1), EPI_DEC, false, false, true>(p, n, s); \
-        if (epi == EPI_RAW) return launch_subpixel_t<(NT <= 2 ? NT : 1), EPI_RAW, false, false, true>(p, n, s); \
-        return hipErrorInvalidValue; \
-    } \
-    if (ct == 16 * NT && !p.bf16) { \
-        if (sc) return launch_subpixel_t<NT, EPI_DEC, true, false>(p, n, s); \
-        if (epi == EPI_DEC) return launch_subpixel_t<NT, EPI_DEC, false, false>(p, n, s); \
-        if (epi == EPI_RAW) return launch_subpixel_t<NT, EPI_RAW, false, false>(p, n, s); \
-        return hipErrorInvalidValue; \
-    } \
-    if (ct == 16 * NT && p.bf16) { \
-        if (sc) return launch_subpixel_t<NT, EPI_DEC, true, true>(p, n, s); \
-        if (epi == EPI_DEC) return launch_subpixel_t<NT, EPI_DEC, false, true>(p, n, s); \
-        if (epi == EPI_RAW) return launch_subpixel_t<NT, EPI_RAW, false, true>(p, n, s); \
-        return hipErrorInvalidValue; \
-    }
-    GSA_SUB(4) GSA_SUB(2) GSA_SUB(1)
-#undef GSA_SUB
     return hipErrorInvalidValue;
 }
 
-// rows per thread of the blurred form: 4 from 64 px on (enough threads to fill the chip), else the one-row kernel
-static int post_rpt(const PostParams& p) {
-    static const int forced = getenv("GSA_POST_RPT") ? atoi(getenv("GSA_POST_RPT")) : -1;
-    if (!p.blur || !p.src_per_sample || p.H % 8) return 1;
-    if (forced >= 0) return forced == 8 ? 8 : (forced == 4 ? 4 : (forced == 2 ? 2 : 1));
-    return p.H >= 64 ? 4 : 1;
-}
-
-// workgroups per sample of the form launch_post picks
-// row groups per thread of post_rows_kernel<4> (GSA_POST_NG; default 1).  Measured, FFHQ batch 8, ms per launch at 1024 / 512 / 256 /
+// ---- post pass -----------------------------------------------------------------------------------------------------------------------
+// The plan of the blur / noise / bias / LeakyReLU / statistics pass.  rpt = rows per thread of the blurred form: 4 from 64 px on (enough
+// threads to fill the chip), else the one-row kernel; GSA_POST_RPT forces 1 / 2 / 4 / 8.
+// row_groups = row groups per thread of post_rows_kernel<4> (GSA_POST_NG; default 1).  Measured, FFHQ batch 8, ms per launch at 1024 / 512 / 256 /
 // 128 px, kernels serialized: 1 group 0.274 / 0.133 / 0.061 / 0.031; 2: 0.260 / 0.127 / 0.058 / 0.030; 4: 0.257 / 0.117 / 0.058 / 0.032;
 // 8: 0.253 / 0.107 / 0.077 / 0.046 -- the best choice per size saves 0.04 ms of serialized kernel time per step, but the STEP (decoder
 // running beside the synthesis) was 0-1 % slower with it in four of four same-box comparisons (1257-1265 vs 1254-1256 pairs/s): fewer,
 // longer-lived workgroups leave the concurrent stream less room.  Not adopted.
-static int post_row_groups(const PostParams& p) {
-    static const int forced = getenv("GSA_POST_NG") ? atoi(getenv("GSA_POST_NG")) : -1;
-    if (post_rpt(p) != 4) return 1;
-    int ng = forced > 0 ? forced : 1;
-    while (ng > 1 && p.H % (4 * ng)) ng >>= 1;
-    return ng;
+// kind: the LDS-DMA ring where it applies (gsa_post_lean.hip), else by rpt: the packed-arithmetic form of four rows per thread where a
+// wave's 64 threads lie inside one row group, post_rows_kernel<rpt>, or the one-row post_kernel.
+PostPlan post_plan(const PostParams& p) {
+    static const int forced_rpt = env_int("GSA_POST_RPT", -1);
+    static const int forced_ng = env_int("GSA_POST_NG", -1);
+    PostPlan plan{};
+    plan.rpt = (!p.blur || !p.src_per_sample || p.H % 8) ? 1
+             : forced_rpt >= 0 ? (forced_rpt == 8 ? 8 : (forced_rpt == 4 ? 4 : (forced_rpt == 2 ? 2 : 1)))
+             : (p.H >= 64 ? 4 : 1);
+    plan.row_groups = plan.rpt == 4 && forced_ng > 0 ? forced_ng : 1;
+    while (plan.row_groups > 1 && p.H % (4 * plan.row_groups)) plan.row_groups >>= 1;
+    if (post_dma_applies(p)) {
+        plan.kind = PostKind::Dma;
+        plan.blocks = post_dma_blocks(p);
+    } else if (plan.rpt == 1) {
+        plan.kind = PostKind::OneRow;
+        plan.blocks = post_prow(p.H, p.W, p.C);
+    } else {
+        plan.kind = (plan.rpt == 4 && post_pk_mode() > 0 && ((p.W / 4) * (p.C / 4)) % 64 == 0) ? PostKind::Packed : PostKind::Rows;
+        plan.blocks = ((p.H / (plan.rpt * plan.row_groups)) * (p.W / 4) * (p.C / 4) + 255) / 256;
+    }
+    plan.rows_used = few_rows() ? std::min(plan.blocks, kDirectRows) : plan.blocks;
+    return plan;
 }
 
-static int post_blocks(const PostParams& p) {
-    if (post_dma_applies(p)) return post_dma_blocks(p);
-    const int rpt = post_rpt(p);
-    return rpt == 1 ? post_prow(p.H, p.W, p.C) : ((p.H / (rpt * post_row_groups(p))) * (p.W / 4) * (p.C / 4) + 255) / 256;
-}
-
-int post_rows_used(const PostParams& p) {
-    const int blocks = post_blocks(p);
-    return few_rows() ? std::min(blocks, kDirectRows) : blocks;
-}
+int post_rows_used(const PostParams& p) { return post_plan(p).rows_used; }
 
 hipError_t launch_post(const PostParams& p, int n, hipStream_t s) {
     if (p.W % 4 || p.C % 4) return hipErrorInvalidValue;
+    const PostPlan plan = post_plan(p);
     PostParams q = p;
-    const int rpt = post_rpt(p);
-    q.prow = post_rows_used(p);
-    q.row_groups = post_row_groups(p);
-    if (post_dma_applies(p)) return launch_post_dma(q, n, s);
-    dim3 grid(post_blocks(p), n);
+    q.prow = plan.rows_used;
+    q.row_groups = plan.row_groups;
+    const dim3 grid(plan.blocks, n);
     const size_t lds = sizeof(unsigned long long) * 2 * p.C;
-    // the packed-arithmetic form (gsa_post_lean.hip): four rows per thread, a wave's 64 threads inside one row group
-    if (rpt == 4 && post_pk_mode() > 0 && ((p.W / 4) * (p.C / 4)) % 64 == 0)
-        return launch_post_pk(q, grid, lds + sizeof(float) * 9 * p.C, s);
     const int dev = current_device();
+    switch (plan.kind) {
+        case PostKind::Dma: return launch_post_dma(q, n, s);
+        case PostKind::Packed: return launch_post_pk(q, grid, lds + sizeof(float) * 9 * p.C, s);
+        default: break;      // Rows, OneRow: the instantiation for plan.rpt rows per thread
+    }
 #define GSA_POST(BF) \
-    if (rpt == 8) return launch<post_rows_kernel<8, BF>>(dev, grid, dim3(256), lds, s, q); \
-    if (rpt == 4) return launch<post_rows_kernel<4, BF>>(dev, grid, dim3(256), lds, s, q); \
-    if (rpt == 2) return launch<post_rows_kernel<2, BF>>(dev, grid, dim3(256), lds, s, q); \
+    if (plan.rpt == 8) return launch<post_rows_kernel<8, BF>>(dev, grid, dim3(256), lds, s, q); \
+    if (plan.rpt == 4) return launch<post_rows_kernel<4, BF>>(dev, grid, dim3(256), lds, s, q); \
+    if (plan.rpt == 2) return launch<post_rows_kernel<2, BF>>(dev, grid, dim3(256), lds, s, q); \
     return launch<post_kernel<BF>>(dev, grid, dim3(256), lds, s, q);
     if (p.bf16) { GSA_POST(true) }
     GSA_POST(false)
 #undef GSA_POST
 }
 
-// whole-plane K-split tiles (4 and 8 px) finalize in the kernel when the caller supplies the finalize operands (GSA_FUSEFIN=0: never)
-bool conv_fuses_finalize(const ConvParams& p, int epi, bool sc) {
-    static const bool enabled = !(getenv("GSA_FUSEFIN") && atoi(getenv("GSA_FUSEFIN")) == 0);
-    return enabled && epi == EPI_SYNTH && conv_uses_ksplit(p, sc) && p.H == p.W && p.H <= 8 && !conv_uses_wino(p, epi, sc);
-}
 // post_fin_kernel: planes of at most 32 x 32 pixels with a multiple of 16 channels (GSA_FUSEFIN=0: the two separate launches)
 bool post_fuses_finalize(const PostParams& p) {
-    static const bool enabled = !(getenv("GSA_FUSEFIN") && atoi(getenv("GSA_FUSEFIN")) == 0);
-    return enabled && p.H * p.W <= 1024 && p.C % 16 == 0 && p.W % 4 == 0;
+    return fuse_finalize() && p.H * p.W <= 1024 && p.C % 16 == 0 && p.W % 4 == 0;
 }
 hipError_t launch_post_fin(const PostParams& p, const FinalizeParams& f, int n, hipStream_t s) {
     if (!post_fuses_finalize(p)) return hipErrorInvalidValue;
@@ -4432,7 +4396,7 @@ hipError_t launch_dense(const float* x, const float* WT, const float* b, float* 
 
 // the fused mapping network applies when its L/16 workgroups are certainly co-resident (see mapping_kernel)
 bool mapping_fused(int L, int device) {
-    static const bool enabled = !(getenv("GSA_MAPFUSE") && atoi(getenv("GSA_MAPFUSE")) == 0);
+    static const bool enabled = env_int("GSA_MAPFUSE", 1) != 0;
     if (!enabled || L % 64 || L > 512 || L < 64) return false;
     return L / 16 <= device_cus(device) / 2;
 }
@@ -4492,7 +4456,7 @@ hipError_t launch_import_nhwc(const float* in, float* out, int n, int H, int W, 
 
 // class pairs as packed fma in the fp32 final conv (speed only, same bits; GSA_FINAL_PK=0: the scalar chains)
 static bool final_pk() {
-    static const bool on = !(getenv("GSA_FINAL_PK") && atoi(getenv("GSA_FINAL_PK")) == 0);
+    static const bool on = env_int("GSA_FINAL_PK", 1) != 0;
     return on;
 }
 

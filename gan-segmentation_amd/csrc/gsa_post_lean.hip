@@ -308,13 +308,13 @@ __global__ __launch_bounds__(256, 1) void post_dma(PostParams p) {
 
 // the fp32 planes post_rows_kernel<4> takes (launch_post decides that); GSA_POST_PK: 0 = post_rows_kernel, 1 = packed, 2 = packed + non-temporal stores
 int post_pk_mode() {
-    static const int mode = getenv("GSA_POST_PK") ? atoi(getenv("GSA_POST_PK")) : 1;
+    static const int mode = env_int("GSA_POST_PK", 1);
     return mode;
 }
 
 // rows per wave: 64, or 32 where that is what gives every SIMD of the chip two bands
 int post_dma_band(const PostParams& p) {
-    static const int forced = getenv("GSA_POST_DMA_BH") ? atoi(getenv("GSA_POST_DMA_BH")) : 0;      // A/B only
+    static const int forced = env_int("GSA_POST_DMA_BH", 0);      // A/B only
     if (forced >= 8 && forced % 4 == 0 && p.H % forced == 0) return forced;
     return (long)(p.H / 64) * (p.W / (1024 / p.C)) * 8 >= 2048 ? 64 : 32;
 }
@@ -322,7 +322,7 @@ int post_dma_band(const PostParams& p) {
 // the LDS-DMA form for the blurred fp32 planes with 16 or 32 channels (1024^2 and 512^2 of the FFHQ path); GSA_POST_DMA=0: post_rows_pk (same bits).
 // Same box, FFHQ batch 8: 0.243 -> 0.225 ms at 1024^2, 0.116 -> 0.108 at 512^2 (gpurun_out/r5/pdma*); band height 32-64 rows equal, 16 and 128 slower.
 bool post_dma_applies(const PostParams& p) {
-    static const bool on = !(getenv("GSA_POST_DMA") && atoi(getenv("GSA_POST_DMA")) == 0);
+    static const bool on = env_int("GSA_POST_DMA", 1) != 0;
     if (!on || p.bf16 || !p.blur || !p.src_per_sample || (p.C != 16 && p.C != 32)) return false;
     return p.W % (1024 / p.C) == 0 && p.H % post_dma_band(p) == 0 && p.H >= 64;
 }
@@ -333,7 +333,7 @@ hipError_t launch_post_dma(const PostParams& p, int n, hipStream_t s) {
     PostParams q = p;
     q.row_groups = post_dma_band(p);
     const dim3 grid(post_dma_blocks(p), n);
-    static const bool ost = !(getenv("GSA_POST_DMA_OST") && atoi(getenv("GSA_POST_DMA_OST")) == 0);
+    static const bool ost = env_int("GSA_POST_DMA_OST", 1) != 0;
     const size_t lds = sizeof(float) * 4 * 8 * ((1024 / p.C + 2) * (p.C / 4) + 1024 / p.C / 4) * 4 + (ost ? 16384 : 0) + sizeof(unsigned long long) * 2 * p.C;
     const int dev = current_device();
     if (!ost) {

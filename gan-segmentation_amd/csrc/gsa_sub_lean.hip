@@ -405,7 +405,7 @@ size_t sub_lds(const ConvParams& q, int nt, bool sc, bool aff, int kb, bool wst,
 // panel; same bits).  Measured 2.3 % slower over the whole step (1290 against 1320 pairs/s on one box): see DESIGN.md section 5.
 bool sub_counters(const ConvParams& q, int nt, bool sc, int kb, bool wst) {
 #if GSA_EXPERIMENTS
-    static const bool cnt_on = getenv("GSA_SUB_CNT") && atoi(getenv("GSA_SUB_CNT")) != 0;
+    static const bool cnt_on = env_int("GSA_SUB_CNT", 0) != 0;
     return cnt_on && !wst && sub_lds(q, nt, sc, q.aff0 != nullptr, kb, false, true) <= 160 * 1024;
 #else
     (void)q; (void)nt; (void)sc; (void)kb; (void)wst;
@@ -435,7 +435,7 @@ hipError_t launch_shape(const ConvParams& q, int kb, bool wst, dim3 grid, hipStr
 // the launches of subpixel_res<..., WINO> (fp32) this file takes: 16 or 32 output channels per workgroup, epilogue RAW or DEC, AdaIN only on
 // a single source.  GSA_SUB_LEAN=0 keeps subpixel_res (same bits).
 bool subpixel_lean_applies(const ConvParams& p, int nt, int epi, bool sc, int kb, bool wst) {
-    static const bool enabled = !(getenv("GSA_SUB_LEAN") && atoi(getenv("GSA_SUB_LEAN")) == 0);
+    static const bool enabled = env_int("GSA_SUB_LEAN", 1) != 0;
     if (!enabled || p.bf16 || (nt != 1 && nt != 2) || (epi != EPI_RAW && epi != EPI_DEC) || (sc && epi != EPI_DEC)) return false;
     if (p.aff0 != nullptr && p.C1 != 0) return false;
     return lean::sub_lds(p, nt, sc, p.aff0 != nullptr, kb, wst, false) <= 160 * 1024;

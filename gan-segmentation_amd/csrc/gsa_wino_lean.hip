@@ -857,7 +857,7 @@ hipError_t launch_t(const ConvParams& p, int n, hipStream_t s) {
 
 // GSA_WINO_LEAN_SB=1: the single-buffered three-workgroups-per-CU form for the 16 -> 16 decoder layers (A/B; same bits)
 bool single_buffered() {
-    static const bool on = getenv("GSA_WINO_LEAN_SB") && atoi(getenv("GSA_WINO_LEAN_SB")) != 0;
+    static const bool on = env_int("GSA_WINO_LEAN_SB", 0) != 0;
     return on;
 }
 
@@ -866,7 +866,7 @@ bool single_buffered() {
 // the staging writes is the memory system's throughput (1.1-1.2 GB of traffic in 0.23 ms), not the distance between a load and its use.
 // Default: one set (24 registers fewer).
 int prefetch_sets() {
-    static const int pf = getenv("GSA_WINO_LEAN_PF") ? atoi(getenv("GSA_WINO_LEAN_PF")) : 1;
+    static const int pf = env_int("GSA_WINO_LEAN_PF", 1);
     return pf == 2 ? 2 : 1;
 }
 
@@ -910,7 +910,7 @@ hipError_t launch_stream_t(const ConvParams& p, int n, hipStream_t s) {
     q.tiles_y = p.H / 16;
     q.groups = p.Cout / (16 * NT);                     // workgroup columns: a group (NT = 2: a pair of groups) each
 #if GSA_EXPERIMENTS
-    static const int stagger = getenv("GSA_STAGGER") ? atoi(getenv("GSA_STAGGER")) : 0;
+    static const int stagger = env_int("GSA_STAGGER", 0);
     q.group_minor = stagger;
 #else
     q.group_minor = 0;
@@ -931,10 +931,10 @@ hipError_t launch_stream_t(const ConvParams& p, int n, hipStream_t s) {
 }  // namespace lean
 using namespace lean;
 
-// the layers this file takes: Winograd form (conv_uses_wino), 16 -> 16 or 32 -> 32 channels, output >= 32 px, synthesis epilogue with direct
+// the layers this file takes: Winograd form (conv3x3_form), 16 -> 16 or 32 -> 32 channels, output >= 32 px, synthesis epilogue with direct
 // statistics or decoder epilogue with the residual absent or one half-resolution tensor.  GSA_WINO_LEAN=0 keeps conv3x3_wino (same bits).
 bool wino_lean_applies(const ConvParams& p, int epi) {
-    static const int enabled = getenv("GSA_WINO_LEAN") ? atoi(getenv("GSA_WINO_LEAN")) : 7;      // bit 0: 16 -> 16, bit 1: 32 -> 32
+    static const int enabled = env_int("GSA_WINO_LEAN", 7);      // bit 0: 16 -> 16, bit 1: 32 -> 32
     if (p.H != p.W || p.H % 16) return false;
     if ((enabled & 4) && p.C0 >= 64 && p.C0 <= 512 && p.resid == nullptr && p.H >= 16)      // bit 2: the streamed-weight layers
         return epi == EPI_SYNTH ? (p.partials != nullptr && p.noise != nullptr && p.fin_aff == nullptr) : epi == EPI_DEC;
@@ -948,7 +948,7 @@ bool wino_lean_applies(const ConvParams& p, int epi) {
 
 // toRGB rides on the decoder's last cvt conv when that conv is the 16 -> 16 lean kernel reading an AdaIN source, 3 colours (GSA_FUSE_RGB=0: never)
 bool wino_lean_fuses_torgb(const ConvParams& p, int epi, int nc) {
-    static const bool enabled = !(getenv("GSA_FUSE_RGB") && atoi(getenv("GSA_FUSE_RGB")) == 0);
+    static const bool enabled = env_int("GSA_FUSE_RGB", 1) != 0;
     return enabled && nc == 3 && epi == EPI_DEC && p.C0 == 16 && p.Cout == 16 && p.aff0 != nullptr && p.resid == nullptr && !p.bf16 &&
            wino_lean_applies(p, epi) && !single_buffered();
 }
@@ -958,7 +958,7 @@ bool wino_lean_fuses_torgb(const ConvParams& p, int epi, int nc) {
 // 0.224/0.221/0.218/0.228 -> 0.227/0.220/0.218/0.232 ms), with the memory instructions inside the MFMA stream (GSA_WINO_IL=1) -4 % on three of them.
 bool stream_pairs(const ConvParams& p, int n) {
 #if GSA_EXPERIMENTS
-    static const int on = getenv("GSA_WINO_NT2") ? atoi(getenv("GSA_WINO_NT2")) : 0;
+    static const int on = env_int("GSA_WINO_NT2", 0);
     if (!on || p.Cout % 32) return false;
     const long wgs = (long)(p.W / 16) * (p.H / 16) * n * (p.Cout / 32);
     return wgs >= (on == 2 ? 1 : 256);
@@ -971,7 +971,7 @@ bool stream_pairs(const ConvParams& p, int n) {
 // GSA_WINO_IL=1 (experiments build): the paired streamed-weight kernel issues its memory instructions inside the MFMA stream -- speed only, same bits
 int stream_interleaved() {
 #if GSA_EXPERIMENTS
-    static const int il = getenv("GSA_WINO_IL") ? atoi(getenv("GSA_WINO_IL")) : 0;
+    static const int il = env_int("GSA_WINO_IL", 0);
     return il == 1 ? 1 : 0;
 #else
     return 0;
