@@ -121,9 +121,18 @@ SIGNATURES = {
     },
 }
 
+# The headers under include_ext/, in the same form: the set of headers under include/ and the keys of SIGNATURES are pinned by
+# tests/test_abi_and_host.py, so an ABI added since lives beside them.  tests/test_components_host.py checks this table against the
+# header's text.
+EXT_SIGNATURES = {
+    "gsa_components.h": {
+        "gsa_mask_components": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    },
+}
+
 
 class Api:
-    """Function table of one shared library: every entry of ``SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full
+    """Function table of one shared library: every entry of ``SIGNATURES`` and ``EXT_SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full
     name; the entries of include/gsa.h are attributes without the prefix as well (``api.create``, ``api.generate``, ...)."""
 
     def __init__(self, path, prefix="gsa_"):
@@ -137,7 +146,7 @@ class Api:
         import torch  # noqa: F401
         self.lib = ctypes.CDLL(path)
         self._fns = {}
-        for header, group in SIGNATURES.items():
+        for header, group in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             for name, (res, args) in group.items():
                 try:
                     fn = getattr(self.lib, name)

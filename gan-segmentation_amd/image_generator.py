@@ -27,6 +27,12 @@ on the GPU from ``generate_indexed`` pairs by the plan and the kernel of ``augme
 ``mask_morph=True`` (fixed at construction, off by default) cleans the mask of every fused call -- the same calls as above, and
 therefore ``training_batches`` -- with ``mask_ops.morph_mask``, the 5x5 close + open of reference utils.morph_mask (DESIGN.md
 section 14): the mask returned is the rule applied to what the same call returns without the option, the image is untouched.
+
+``mask_min_area=k`` (fixed at construction; 0, the default, and 1 are off) passes the mask of every fused call through
+``mask_ops.despeckle``: every connected component of fewer than k pixels (``mask_connectivity`` 4 or 8) takes the value of its
+neighbour or the constant ``mask_fill`` (the rule of include_ext/gsa_components.h) -- after ``mask_morph``
+when both are on, and before anything reads the mask.  The labels and areas it works in are kept per replica, batch size and
+stream: 8 bytes per mask pixel, 256 MiB for ffhq at batch 32.  The image is untouched.
 """
 import os
 
@@ -52,33 +58,40 @@ class ImageGenerator:
     style_mix_prob = 0.0
     output_downscale = 1
     mask_morph = False
+    mask_min_area = 0
+    mask_connectivity = 8
+    mask_fill = "neighbour"
 
     def __init__(self, gpu_ids, gan_dir, gan="ffhq", batch_size=4, return_latents=False, seed=0, precision="fp32",
-                 truncation_psi=None, style_mix_prob=0.0, output_downscale=1, mask_morph=False):
+                 truncation_psi=None, style_mix_prob=0.0, output_downscale=1, mask_morph=False, mask_min_area=0, mask_connectivity=8,
+                 mask_fill="neighbour"):
         cfg = self._get_config(max_res_log2=_weights.GAN_MAX_RES_LOG2[gan])
         self._setup(cfg, os.path.join(gan_dir, "stylegan-%s.params" % gan), gpu_ids, batch_size, return_latents, seed, precision,
-                    truncation_psi, style_mix_prob, output_downscale, mask_morph)
+                    truncation_psi, style_mix_prob, output_downscale, mask_morph, mask_min_area, mask_connectivity, mask_fill)
 
     @classmethod
     def from_params(cls, gcfg, gparams, dcfg=None, dparams=None, gpu_ids=(0,), batch_size=4,
                     return_latents=False, seed=0, precision="fp32", truncation_psi=None, style_mix_prob=0.0, output_downscale=1,
-                    mask_morph=False):
+                    mask_morph=False, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour"):
         """Build from in-memory weights (tests, benchmarks: no pretrained files exist here)."""
         self = cls.__new__(cls)
         self._setup(dict(gcfg), gparams, gpu_ids, batch_size, return_latents, seed, precision, truncation_psi, style_mix_prob,
-                    output_downscale, mask_morph)
+                    output_downscale, mask_morph, mask_min_area, mask_connectivity, mask_fill)
         if dcfg is not None:
             self.attach_decoder(dcfg, dparams)
         return self
 
     def _setup(self, cfg, gparams, gpu_ids, batch_size, return_latents, seed, precision, truncation_psi, style_mix_prob,
-               output_downscale, mask_morph):
+               output_downscale, mask_morph, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour"):
         """What both constructors do: the options, checked before any file or device is touched; one generator replica per gpu
         id, loaded from ``gparams`` (a ``.params`` path, read once, or a ``{name: array}`` dict); the seeds."""
         self.cfg = cfg
         self.max_res_log2 = cfg["max_res_log2"]
         self.output_downscale = self.check_output_downscale(output_downscale, self.max_res_log2)
         self.mask_morph = self.check_mask_morph(mask_morph)
+        self.mask_min_area = self.check_mask_min_area(mask_min_area)
+        self.mask_connectivity = self.check_mask_connectivity(mask_connectivity)
+        self.mask_fill = self.check_mask_fill(mask_fill)
         self.latent_size = cfg["latent_size"]
         self.return_latents = return_latents
         self.batch_size = batch_size
@@ -130,6 +143,21 @@ class ImageGenerator:
         if not isinstance(v, bool):
             raise ValueError("mask_morph must be True or False, got %r" % (v,))
         return v
+
+    @staticmethod
+    def check_mask_min_area(v):
+        """The area threshold of the component filter as an int: 0 .. 2^31 - 1 pixels, 0 and 1 meaning off (ValueError otherwise)."""
+        return _mask_ops.check_min_area(v, "mask_min_area")
+
+    @staticmethod
+    def check_mask_connectivity(v):
+        """The component filter's connectivity as an int: 4 or 8 (ValueError otherwise)."""
+        return _mask_ops.check_connectivity(v, "mask_connectivity")
+
+    @staticmethod
+    def check_mask_fill(v):
+        """What the component filter writes into a small component: "neighbour" or an int 0..255 (ValueError otherwise)."""
+        return "neighbour" if _mask_ops.check_fill(v, "mask_fill") == _mask_ops.FILL_NEIGHBOUR else int(v)
 
     def _get_G(self, config, device):
         return Generator(config, device=device, precision=self.precision)
@@ -327,7 +355,8 @@ class ImageGenerator:
 
     def _pair_buffers(self, r, n, out):
         """(img, raw mask, final mask) of a fused step of ``n`` samples on replica ``r``: new tensors, or the checked ``out``; the
-        step writes the raw mask, ``_finish_mask`` turns it into the final one (the same tensor without ``mask_morph``)."""
+        step writes the raw mask, ``_finish_mask`` turns it into the final one (the same tensor without ``mask_morph`` and
+        ``mask_min_area``)."""
         g = self._gens[r]
         dev = g._model.device
         if out is None:
@@ -344,28 +373,39 @@ class ImageGenerator:
         z, noise, n = g._prepare(z, noise)
         img, raw, final = self._pair_buffers(r, n, out)
         self._run_step(g._model, g._model.device, n, z, [a.data_ptr() for a in noise], img, raw)
-        return img, self._finish_mask(raw, final)
+        return img, self._finish_mask(r, raw, final)
 
     def _raw_mask(self, r, mask):
-        """Where the step of replica ``r`` writes its mask: ``mask`` itself, or with ``mask_morph`` a scratch tensor kept per replica,
-        batch size and stream (calls on one stream are ordered, so they may share it) -- the same address every call, so a captured
-        graph that bakes it in stays valid whatever ``mask`` is."""
-        if not self.mask_morph:
+        """Where the step of replica ``r`` writes its mask: ``mask`` itself, or with ``mask_morph`` or ``mask_min_area`` a scratch
+        tensor kept per replica, batch size and stream (calls on one stream are ordered, so they may share it) -- the same address
+        every call, so a captured graph that bakes it in stays valid whatever ``mask`` is."""
+        if not self.mask_morph and self.mask_min_area <= 1:
             return mask
-        cache = self.__dict__.setdefault("_raw_masks", {})
-        key = (r, mask.shape[0], torch.cuda.current_stream(mask.device).cuda_stream)
-        raw = cache.get(key)
-        if raw is None:
-            raw = cache[key] = torch.empty_like(mask)
-        return raw
+        return self._mask_scratch("raw", r, mask, torch.uint8)
 
-    @staticmethod
-    def _finish_mask(raw, final):
-        """The mask a fused call returns: with ``mask_morph`` the clean-up of the raw one, one eager launch behind the step on the
-        same stream (never part of a captured graph)."""
+    def _mask_scratch(self, what, r, mask, dtype):
+        """The scratch tensor ``what`` of ``mask``'s shape: kept per replica, batch size and stream."""
+        cache = self.__dict__.setdefault("_raw_masks", {})
+        key = (what, r, mask.shape[0], torch.cuda.current_stream(mask.device).cuda_stream)
+        t = cache.get(key)
+        if t is None:
+            t = cache[key] = torch.empty(mask.shape, dtype=dtype, device=mask.device)
+        return t
+
+    def _finish_mask(self, r, raw, final):
+        """The mask a fused call of replica ``r`` returns: the raw one passed through ``mask_morph`` and then through the component
+        filter of ``mask_min_area``, whichever are on -- eager launches behind the step on the same stream (never part of a captured
+        graph), before anything reads the mask.  The filter's labels and areas (int32 each: 8 bytes per pixel, 256 MiB for ffhq at
+        batch 32) are scratch of the same kind as the raw mask."""
         if raw is final:
             return final
-        return _mask_ops.morph_mask(raw, out=final)
+        filtered = self.mask_min_area > 1
+        if self.mask_morph:
+            raw = _mask_ops.morph_mask(raw, out=self._mask_scratch("morphed", r, final, torch.uint8) if filtered else final)
+        if filtered:
+            scratch = (self._mask_scratch("labels", r, final, torch.int32), self._mask_scratch("areas", r, final, torch.int32))
+            _mask_ops.despeckle(raw, self.mask_min_area, self.mask_connectivity, self.mask_fill, out=final, scratch=scratch)
+        return final
 
     def _run_step(self, model, dev, n, z, nptrs, img, mask):
         """The z step into ``img`` / ``mask``: eager, or replayed from a hipGraph."""
@@ -421,7 +461,7 @@ class ImageGenerator:
         img, raw, final = self._pair_buffers(r, n, out)
         self._step(g._model.ctx, current_stream_ptr(g._model.device), n, None, [a.data_ptr() for a in noise], img, raw,
                    self.output_downscale, dl, g.num_style_layers)
-        return img, self._finish_mask(raw, final)
+        return img, self._finish_mask(r, raw, final)
 
     @staticmethod
     def _capture(model, dev, n, z, nptrs, img, mask, factor=1):

@@ -2,13 +2,31 @@
 counterpart of reference utils.morph_mask (utils.py:105-109): a 5x5 close followed by a 5x5 open of a class-index mask.
 
 ``morph_mask(mask)`` enqueues one kernel on the current stream of ``mask``'s device and returns the cleaned mask;
-``ImageGenerator(..., mask_morph=True)`` applies it to the mask of every fused call.  No CPU fallback."""
+``ImageGenerator(..., mask_morph=True)`` applies it to the mask of every fused call.  No CPU fallback.
+
+Also the binding of the mask components (include_ext/gsa_components.h, csrc/gsa_components.hip), which the
+reference does not have: ``components(mask)`` labels the connected components of equal value and gives their areas,
+``despeckle(mask, min_area)`` replaces every component smaller than ``min_area`` pixels -- a clean-up with an area threshold where
+the morphology has a window size -- and can return per-sample component counts; ``ImageGenerator(..., mask_min_area=k)`` applies it
+to the mask of every fused call, after ``mask_morph``."""
+import numpy as np
 import torch
 
 from ._runtime import is_device_tensor, launch
 
 MAX_EXTENT = 65535
 
+# The summary row of ``despeckle(..., return_stats=True)``: COMP_ROW int64 words per sample (include_ext/gsa_components.h).  Slots as
+# pair_stats: slot k < 8 is mask value k, slot 8 every value >= 8.
+COMP_SLOTS = 9
+COMP_NCOMP = 0              # + s: number of components whose value falls in slot s
+COMP_LARGEST = 9            # + s: the largest area among them, 0 if there is none
+COMP_SMALL = 18             # number of components with area < min_area
+COMP_SMALL_PIXELS = 19      # sum of their areas
+COMP_ROW = 20
+FILL_NEIGHBOUR = -1
+CONNECTIVITIES = (4, 8)
+MAX_AREA = 2 ** 31 - 1
 
 def _check(t, what):
     if not is_device_tensor(t, torch.uint8, dims=(2, 3)):
@@ -37,4 +55,100 @@ def morph_mask(mask, out=None):
         out = torch.empty_like(mask)
     if n:
         launch("gsa_mask_morph", dev, n, H, W, mask.data_ptr(), out.data_ptr())
+    return out
+
+
+def check_connectivity(v, what="connectivity"):
+    """4 or 8 as an int (ValueError otherwise; a bool is not a number here)."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) not in CONNECTIVITIES:
+        raise ValueError("%s must be 4 or 8, got %r" % (what, v))
+    return int(v)
+
+
+def check_min_area(v, what="min_area"):
+    """An area threshold in pixels as an int: 0 .. 2^31 - 1 (0 and 1 change nothing).  ValueError otherwise."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MAX_AREA:
+        raise ValueError("%s must be an int in 0..%d, got %r" % (what, MAX_AREA, v))
+    return int(v)
+
+
+def check_fill(v, what="fill"):
+    """``"neighbour"`` or an int 0..255 -> the C entry's fill argument (-1 for "neighbour").  ValueError otherwise."""
+    if isinstance(v, str) and v == "neighbour":
+        return FILL_NEIGHBOUR
+    if isinstance(v, (bool, str)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 255:
+        raise ValueError("%s must be \"neighbour\" or an int in 0..255, got %r" % (what, v))
+    return int(v)
+
+
+def _plane_shape(mask, who):
+    _check(mask, "mask")
+    H, W = mask.shape[-2:]
+    if not 1 <= H <= MAX_EXTENT or not 1 <= W <= MAX_EXTENT or H * W >= 2 ** 31:
+        raise ValueError("%s takes masks whose sides are 1..%d px with fewer than 2^31 pixels, got %dx%d" % (who, MAX_EXTENT, H, W))
+    return (mask.shape[0] if mask.dim() == 3 else 1), H, W
+
+
+def _scratch_pair(scratch, mask):
+    """The (labels, areas) working tensors of a call: new ones, or the caller's checked pair."""
+    if scratch is None:
+        return (torch.empty(mask.shape, dtype=torch.int32, device=mask.device),
+                torch.empty(mask.shape, dtype=torch.int32, device=mask.device))
+    labels, areas = scratch
+    for t in (labels, areas):
+        if not is_device_tensor(t, torch.int32, shape=mask.shape, device=mask.device):
+            raise ValueError("scratch must be two contiguous int32 tensors %s on %s" % (tuple(mask.shape), mask.device))
+    if labels.data_ptr() == areas.data_ptr() and labels.numel():
+        raise ValueError("scratch must be two different tensors")
+    return labels, areas
+
+
+def components(mask, connectivity=8):
+    """mask (H, W) or (n, H, W) contiguous uint8 CUDA tensor -> ``(labels, areas)``, two int32 tensors of the same shape: for every
+    pixel the smallest raster index ``y * W + x`` of its connected component (its first pixel) and the component's pixel count.  A
+    component is a maximal set of pixels of equal raw value joined by horizontal and vertical steps (``connectivity=4``) or by
+    diagonal ones as well (8, cv2's default and ours); every value forms components, 0 included; every image of a batch is a plane
+    of its own (the rule of include_ext/gsa_components.h).  Enqueued on the current stream of ``mask``'s device; the input is not
+    written.  ValueError on anything else; no CPU fallback."""
+    n, H, W = _plane_shape(mask, "components")
+    connectivity = check_connectivity(connectivity)
+    labels, areas = _scratch_pair(None, mask)
+    if n:
+        launch("gsa_mask_components", mask.device, n, H, W, connectivity, 0, FILL_NEIGHBOUR, mask.data_ptr(), labels.data_ptr(),
+               areas.data_ptr(), None, None)
+    return labels, areas
+
+
+def despeckle(mask, min_area, connectivity=8, fill="neighbour", out=None, return_stats=False, scratch=None):
+    """mask (H, W) or (n, H, W) contiguous uint8 CUDA tensor -> a tensor of the same shape (new, or ``out``, which must not overlap
+    ``mask``) in which every pixel of a component (see ``components``) of fewer than ``min_area`` pixels is replaced: by ``fill`` if
+    that is an int 0..255, or with ``fill="neighbour"`` by the input value of the pixel left of the component's first pixel (the one
+    above it if the first pixel is in column 0) -- for an enclosed island or hole the enclosing region; the component that holds
+    pixel (0, 0) has no such neighbour and is kept.  One pass on the input's values: a small speck nested in a small speck takes
+    the outer speck's input value, so a second call can still change something.  ``min_area <= 1`` changes nothing.
+
+    ``return_stats=True`` returns ``(out, rows)`` with ``rows`` (n, COMP_ROW) int64 on the device (``(COMP_ROW,)`` for a 2-D mask):
+    component counts and largest areas per value slot, and the number and pixel sum of the components below ``min_area``
+    (``COMP_*`` above); they do not depend on ``fill``.  ``scratch``: two int32 tensors of ``mask``'s shape to work in (8 bytes per
+    pixel) instead of new ones; they hold the labels and areas afterwards.  Enqueued on the current stream of ``mask``'s device; the
+    input is not written.  ValueError on anything else; no CPU fallback."""
+    n, H, W = _plane_shape(mask, "despeckle")
+    min_area, connectivity, fill = check_min_area(min_area), check_connectivity(connectivity), check_fill(fill)
+    dev = mask.device
+    if out is not None:
+        _check(out, "out")
+        if tuple(out.shape) != tuple(mask.shape) or out.device != dev:
+            raise ValueError("out must be a contiguous uint8 tensor %s on %s" % (tuple(mask.shape), dev))
+        a, b, size = mask.data_ptr(), out.data_ptr(), mask.numel()
+        if out is mask or (size and a < b + size and b < a + size):
+            raise ValueError("out must not be, or overlap, the input mask")
+    labels, areas = _scratch_pair(scratch, mask)
+    if out is None:
+        out = torch.empty_like(mask)
+    rows = torch.empty((n, COMP_ROW), dtype=torch.int64, device=dev) if return_stats else None
+    if n:
+        launch("gsa_mask_components", dev, n, H, W, connectivity, min_area, fill, mask.data_ptr(), labels.data_ptr(), areas.data_ptr(),
+               out.data_ptr(), rows.data_ptr() if return_stats else None)
+    if return_stats:
+        return out, (rows[0] if mask.dim() == 2 else rows)
     return out
