@@ -118,6 +118,10 @@ bool wino43_enabled();                                              // GSA_WINO4
 // gsa_wino_lean.hip (round 5): the Winograd layers with one 16-channel input block and one 16-channel output group in a leaner
 // instruction stream -- speed only, the same arithmetic and bits as conv3x3_wino (GSA_WINO_LEAN=0 keeps conv3x3_wino)
 bool wino_lean_applies(const ConvParams& p, int epi);
+// ... and, inside that form, which of its two streamed-weight kernels (>= 64 input channels) a launch of n samples runs: true = the paired
+// one (conv3x3_wino_stream_pair: one 8-wave workgroup stages each tile once for two output groups), when Cout % 32 == 0 and
+// tiles x n x (Cout / 32) >= CUs; GSA_WINO_PAIR = 0 never, 2 wherever Cout % 32 == 0.  The one statement of the rule: the launcher asks it
+bool wino_stream_paired(const ConvParams& p, int n);
 hipError_t launch_wino_lean(const ConvParams& p, int epi, int n, hipStream_t s);
 bool wino_lean_fuses_torgb(const ConvParams& p, int epi, int nc);      // the lean kernel's own conditions
 bool conv_fuses_torgb(const ConvParams& p, int epi, bool shortcut, int nc);      // true: launch_conv3x3 on p (rgb_* set) also produces toRGB's uint8 image

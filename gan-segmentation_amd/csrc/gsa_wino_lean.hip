@@ -478,19 +478,30 @@ __device__ __forceinline__ void antiphase_start(int cycles64, float* lds_word) {
 // scheduling barriers that pin the memory instructions also stop the compiler from hoisting them.
 // (A further form, IL = 2 -- the item's barrier moved between the staging stores and the MFMAs so that the next item's patch reads could be
 // issued in front of the MFMAs and transformed behind them -- was bit-exact and 12 % slower without spills, 55 % slower with them: DESIGN.md 5.)
-template <int EPI, bool AFF, int NT = 1, int IL = 0>
-__global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(ConvParams p) {
-    constexpr int NCH = 6;
+// PAIR (NT = 1, IL = 0; conv3x3_wino_stream_pair): the TWO workgroups of a CU that run output groups 2y and 2y + 1 over the same tile range
+// become ONE workgroup of 8 waves.  Waves 0-3 (quad 0) and 4-7 (quad 1) each are the four waves of the unpaired kernel for their group: own
+// weight ring, own epilogue row, own statistics -- the same patch reads, transform, MFMA chains and epilogue per wave, hence the same bits.
+// What the quads share is what the unpaired workgroups did twice on the same input: the halo image is loaded, AdaIN-applied and stored to
+// LDS ONCE, by all 512 threads (3 chunks per thread instead of 6), beside the coefficient table, the tile walk and the closing barrier.
+// Still two waves per SIMD: 110 KB of LDS, one workgroup per CU.
+template <int EPI, bool AFF, int NT, int IL, bool PAIR>
+__device__ __forceinline__ void wino_stream_body(const ConvParams& p) {
+    static_assert(!PAIR || (NT == 1 && IL == 0), "paired form: one group per wave quad, phased memory instructions");
+    constexpr int NTHR = PAIR ? 512 : 256;
+    constexpr int NCH = (NPIX * 4 + NTHR - 1) / NTHR;      // staging rounds per item: 6 (5 full + 16 chunks) with 256 threads, 3 (2 full + 272) with 512
+    constexpr int NP = PAIR ? 2 : NT;                      // weight panels per ring buffer = output groups of the workgroup
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* const sA = smem;                       // [2][IMG]
-    float* const sB = smem + 2 * IMG;             // [2][NT][SEG]
-    float* const sE = sB + 2 * NT * SEG;          // [NT][4][16]: nscale | nbias | bn_s | bn_beta of the group's 16 output channels
-    float* const sC = sE + 64 * NT;               // [nblk][32]: A of the block's 16 channels, then B (the sample being staged)
+    float* const sB = smem + 2 * IMG;             // [2][NP][SEG]
+    float* const sE = sB + 2 * NP * SEG;          // [NP][4][16]: nscale | nbias | bn_s | bn_beta of the group's 16 output channels
+    float* const sC = sE + 64 * NP;               // [nblk][32]: A of the block's 16 channels, then B (the sample being staged)
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = PAIR ? wave8 & 3 : wave8;    // wave of its quad: the tile quadrant, the DMA pieces
+    const int quad = PAIR ? wave8 >> 2 : 0;       // PAIR: which of the workgroup's two output groups
     const int i16 = lane & 15, kq = lane >> 4, part = tid & 3;
     const int H = p.H, W = p.W, CIN = p.C0, COUT = p.Cout, nblk = p.C0 >> 4;
-    const int g = blockIdx.y;
+    const int g = PAIR ? 2 * (int)blockIdx.y + quad : (int)blockIdx.y;
     const int per = (p.total_tiles + (int)gridDim.x - 1) / (int)gridDim.x;
     const int w_begin = xcd_block(blockIdx.x, gridDim.x) * per;
     const int w_end = min(p.total_tiles, w_begin + per);
@@ -504,7 +515,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
     int l_off[NCH];
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
-        const int pix = (tid + 256 * k) >> 2;
+        const int pix = (tid + NTHR * k) >> 2;
         const bool real = pix < NPIX;
         const int ly = real ? pix / LW : 1, lx = real ? pix % LW : 1;
         s_off[k] = (unsigned)(((ly * W + lx) * CIN + part * 4) * 4);
@@ -518,7 +529,8 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
     f32x4 ra[NCH];                                // the item in flight: this thread's activation chunks
     int dbg_items = 0; (void)dbg_items;           // diagnostic build: the first two items always run in full (valid data in both LDS buffers)
     const float* const wgrp = p.wpk + (size_t)g * NT * nblk * SEG + lane * 4;
-    // the item's weight block(s): pieces wave, wave + 4, wave + 8, wave + 12 of 1 KB each per group, straight into the LDS panel
+    // the item's weight block(s): pieces wave, wave + 4, wave + 8, wave + 12 of 1 KB each per group, straight into the LDS panel (PAIR: the
+    // quad's own panel of the ring buffer, filled by the quad's four waves)
     auto dma_weights = [&](int cb, int buf) {
 #ifdef GSA_DBG_HOOKS
         if (p.dbg & 16) cb = 0;      // diagnostic build only (WRONG results): the weight stream stays in L2
@@ -531,7 +543,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
             for (int j = 0; j < 4; ++j) {
                 const int piece = wave + 4 * j;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wb + piece * 256),
-                                                 (__attribute__((address_space(3))) void*)(sB + (buf * NT + ct) * SEG + piece * 256), 16, 0, 0);
+                                                 (__attribute__((address_space(3))) void*)(sB + (PAIR ? buf * 2 + quad : buf * NT + ct) * SEG + piece * 256), 16, 0, 0);
             }
         }
     };
@@ -556,7 +568,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
     int n_coef = -1;
     auto coefficients = [&](int n) {              // wave-uniform and rare: the sample changes (first item; a range spans few samples)
         __syncthreads();                          // nobody still reads the old table
-        for (int e = tid; e < CIN; e += 256) {
+        for (int e = tid; e < CIN; e += NTHR) {
             const f32x4 a = *reinterpret_cast<const f32x4*>(p.aff0 + (size_t)n * CIN + e);      // (mean, A, B, -)
             sC[(e >> 4) * 32 + (e & 15)] = a[1];
             sC[(e >> 4) * 32 + 16 + (e & 15)] = a[2];
@@ -595,9 +607,9 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
     const int bbase = (kq * 16 + i16) * 4;
     const int co4 = g * NT * 16 + kq * 4;
     const unsigned out_off = (unsigned)((((qy * 8 + 2 * wty) * W + qx * 8 + 2 * wtx) * COUT + co4) * 4);
-    if (tid < 16 * NT) {      // the groups' per-channel epilogue constants: read from LDS in the epilogue (one per tile), not held in registers
+    if (tid < 16 * NP) {      // the groups' per-channel epilogue constants: read from LDS in the epilogue (one per tile), not held in registers
         float* e = sE + (tid >> 4) * 64 + (tid & 15);
-        const int co = g * NT * 16 + tid;
+        const int co = (int)blockIdx.y * NP * 16 + tid;      // row tid >> 4 = group ct (PAIR: quad)
         e[0] = EPI == EPI_SYNTH ? p.nscale[co] : 0.f;
         e[16] = EPI == EPI_SYNTH ? p.nbias[co] : 0.f;
         e[32] = EPI == EPI_DEC ? p.bn_s[co] : 0.f;
@@ -647,7 +659,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
         }
 #endif
         const float* a_img = sA + buf * IMG + pbase;
-        const float* b_img = sB + buf * NT * SEG + bbase;
+        const float* b_img = PAIR ? sB + (buf * 2 + quad) * SEG + bbase : sB + buf * NT * SEG + bbase;
         f32x4 V[16];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -733,7 +745,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
         y[0][0] = add4(add4(s0[0], s0[1]), s0[2]); y[0][1] = sub4(sub4(s0[1], s0[2]), s0[3]);
         y[1][0] = add4(add4(s1[0], s1[1]), s1[2]); y[1][1] = sub4(sub4(s1[1], s1[2]), s1[3]);
         char* ob = reinterpret_cast<char*>(p.out) + (((long)(t.n * H + t.y0) * W + t.x0) * COUT + ct * 16) * 4;
-        const float* sEc = sE + ct * 64 + kq * 4;
+        const float* sEc = sE + (PAIR ? quad : ct) * 64 + kq * 4;
         const f32x4 e0 = *reinterpret_cast<const f32x4*>(sEc), e1 = *reinterpret_cast<const f32x4*>(sEc + 16);
         const f32x4 e2 = *reinterpret_cast<const f32x4*>(sEc + 32), e3 = *reinterpret_cast<const f32x4*>(sEc + 48);
 #pragma unroll
@@ -789,10 +801,16 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
     load_item(tc, ec, 0);
     write_item(tc, ec, 0, 0);
     tr = tc; er = ec;
+    // "at most NCH vector-memory operations outstanding": this thread's NCH activation loads of the item in flight are the youngest loads
+    auto wait_all_but_loads = [&]() {
+        static_assert(NCH == 6 || NCH == 3, "the counted wait is spelled per staging-round count");
+        if constexpr (NCH == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+    };
     if (items > 1) {
         next_item(tr, er, cbr);
         load_item(tr, er, cbr);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // the four DMA pieces are older than the six loads of the second item
+        wait_all_but_loads();      // the four DMA pieces are older than the NCH (six; PAIR: three) loads of the second item
     } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -823,8 +841,11 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
         TICK(k4);
         // this wave's DMA pieces have landed before anybody passes the barrier: they are older than the six loads of item it + 2 (in-order
         // completion), so at most six outstanding operations means the pieces are in LDS and the younger loads stay in flight; an
-        // iteration that issued no such loads (the last two) waits for everything
-        if (it + 2 < items) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        // iteration that issued no such loads (the last two) waits for everything.  PAIR: the instruction order of an iteration is the
+        // same -- four DMA pieces, [two noise loads], the item's activation loads, [the epilogue's stores and atomics] -- with THREE
+        // activation loads per thread (1296 chunks over 512 threads), so the count is three: of 4 + x + 3 operations at most x are not
+        // loads, loads complete in order, hence 4 + x completions include the four pieces whichever x complete early
+        if (it + 2 < items) wait_all_but_loads();
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         TICK(k5);
@@ -833,6 +854,17 @@ __global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(Conv
     }
     TFLUSH(6, sw); TFLUSH(7, sl); TFLUSH(8, sm); TFLUSH(9, se); TFLUSH(10, sb);
     TFLUSH(12, (unsigned long long)items); TFLUSH(15, 1ull);
+}
+
+template <int EPI, bool AFF, int NT = 1, int IL = 0>
+__global__ __launch_bounds__(256, NT == 1 ? 2 : 1) void conv3x3_wino_stream(ConvParams p) {
+    wino_stream_body<EPI, AFF, NT, IL, false>(p);
+}
+
+// blockIdx.y = a PAIR of output groups; 512 threads, one workgroup per CU (two waves per SIMD, as two workgroups of conv3x3_wino_stream)
+template <int EPI, bool AFF>
+__global__ __launch_bounds__(512, 1) void conv3x3_wino_stream_pair(ConvParams p) {
+    wino_stream_body<EPI, AFF, 1, 0, true>(p);
 }
 
 template <int EPI, bool AFF, bool RES, int NB, int GW, bool DB = true, int PF = 1, bool RGB = false>
@@ -899,19 +931,20 @@ hipError_t launch_shape(const ConvParams& p, int epi, int n, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-template <int EPI, bool AFF, int NT = 1, int IL = 0>
+template <int EPI, bool AFF, int NT = 1, int IL = 0, bool PAIR = false>
 hipError_t launch_stream_t(const ConvParams& p, int n, hipStream_t s) {
+    constexpr int NP = PAIR ? 2 : NT;                  // output groups per workgroup
     const int nblk = p.C0 / 16;
-    const size_t lds = sizeof(float) * (2 * IMG + 2 * NT * SEG + 64 * NT + nblk * 32);
+    const size_t lds = sizeof(float) * (2 * IMG + 2 * NP * SEG + 64 * NP + nblk * 32);      // PAIR at 512 input channels: 110 KB
     const int cus = device_cus(p.device);
     ConvParams q = p;
     q.wpk = p.wino;
     q.tiles_x = p.W / 16;
     q.tiles_y = p.H / 16;
-    q.groups = p.Cout / (16 * NT);                     // workgroup columns: a group (NT = 2: a pair of groups) each
+    q.groups = p.Cout / (16 * NP);                     // workgroup columns: a group (NT = 2, PAIR: a pair of groups) each
 #if GSA_EXPERIMENTS
     static const int stagger = env_int("GSA_STAGGER", 0);
-    q.group_minor = stagger;
+    q.group_minor = PAIR ? 0 : stagger;
 #else
     q.group_minor = 0;
 #endif
@@ -921,11 +954,12 @@ hipError_t launch_stream_t(const ConvParams& p, int n, hipStream_t s) {
         q.prow = kDirectRows;
         if (p.stat_rows_host) *p.stat_rows_host = q.prow;
     }
-    // persistent workgroups, two per CU (NT = 2: one), each inside its channel group; workgroup (x, g) has the linear index x + g * gx: with gx a
+    // persistent workgroups, two per CU (NT = 2, PAIR: one), each inside its channel group; workgroup (x, g) has the linear index x + g * gx: with gx a
     // multiple of 8 the groups of a tile range meet in one XCD's L2 (conv3x3_wino's launch shape)
-    const int slots = std::max(1, cus * (NT == 1 ? 2 : 1) / q.groups);
+    const int slots = std::max(1, cus * (NP == 1 ? 2 : 1) / q.groups);
     const int gx = std::min(q.total_tiles, slots);
-    return launch<conv3x3_wino_stream<EPI, AFF, NT, IL>>(p.device, dim3(gx, q.groups), dim3(256), lds, s, q);
+    if constexpr (PAIR) return launch<conv3x3_wino_stream_pair<EPI, AFF>>(p.device, dim3(gx, q.groups), dim3(512), lds, s, q);
+    else return launch<conv3x3_wino_stream<EPI, AFF, NT, IL>>(p.device, dim3(gx, q.groups), dim3(256), lds, s, q);
 }
 
 }  // namespace lean
@@ -951,6 +985,17 @@ bool wino_lean_fuses_torgb(const ConvParams& p, int epi, int nc) {
     static const bool enabled = env_int("GSA_FUSE_RGB", 1) != 0;
     return enabled && nc == 3 && epi == EPI_DEC && p.C0 == 16 && p.Cout == 16 && p.aff0 != nullptr && p.resid == nullptr && !p.bf16 &&
            wino_lean_applies(p, epi) && !single_buffered();
+}
+
+// The paired form of the streamed-weight kernel (conv3x3_wino_stream_pair) takes a streamed layer whose output groups pair up and that still
+// gives every CU a workgroup at this batch: 16x16 tiles x n x (Cout / 32) >= CUs; below that the unpaired kernel's twice as many, half as
+// large workgroups fill the chip better.  Monotone in n: one threshold per layer.  GSA_WINO_PAIR: 1 (default) = this rule, 0 = never,
+// 2 = wherever Cout % 32 == 0 (what the tests use to reach the kernel at small shapes).  Speed only, same bits.
+bool wino_stream_paired(const ConvParams& p, int n) {
+    static const int mode = env_int("GSA_WINO_PAIR", 1);
+    if (mode <= 0 || p.C0 < 64 || p.Cout % 32) return false;
+    if (mode == 2) return true;
+    return (long)(p.W / 16) * (p.H / 16) * n * (p.Cout / 32) >= device_cus(p.device);
 }
 
 // GSA_WINO_NT2=1 (experiments build; 2: on every streamed layer): two output groups per workgroup in the streamed-weight kernel -- one wave per
@@ -994,6 +1039,11 @@ hipError_t launch_wino_lean(const ConvParams& p, int epi, int n, hipStream_t s) 
             return hipErrorInvalidValue;
         }
 #endif
+        if (wino_stream_paired(p, n)) {
+            if (epi == EPI_SYNTH) return p.aff0 ? launch_stream_t<EPI_SYNTH, true, 1, 0, true>(p, n, s) : launch_stream_t<EPI_SYNTH, false, 1, 0, true>(p, n, s);
+            if (epi == EPI_DEC) return p.aff0 ? launch_stream_t<EPI_DEC, true, 1, 0, true>(p, n, s) : launch_stream_t<EPI_DEC, false, 1, 0, true>(p, n, s);
+            return hipErrorInvalidValue;
+        }
         if (epi == EPI_SYNTH) return p.aff0 ? launch_stream_t<EPI_SYNTH, true>(p, n, s) : launch_stream_t<EPI_SYNTH, false>(p, n, s);
         if (epi == EPI_DEC) return p.aff0 ? launch_stream_t<EPI_DEC, true>(p, n, s) : launch_stream_t<EPI_DEC, false>(p, n, s);
         return hipErrorInvalidValue;
