@@ -130,9 +130,18 @@ EXT_SIGNATURES = {
     },
 }
 
+# The headers under include_ops/, in the same form.  The file list of include_ext/ and the keys of EXT_SIGNATURES are pinned as well
+# (tests/test_components_host.py); tests/test_boundary_host.py checks the listing of include_ops/ against the keys of THIS table and
+# every header's text against its group, so the next header needs a file and a group here, no fourth directory.
+OPS_SIGNATURES = {
+    "gsa_boundary.h": {
+        "gsa_mask_boundary": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    },
+}
+
 
 class Api:
-    """Function table of one shared library: every entry of ``SIGNATURES`` and ``EXT_SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full
+    """Function table of one shared library: every entry of ``SIGNATURES``, ``EXT_SIGNATURES`` and ``OPS_SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full
     name; the entries of include/gsa.h are attributes without the prefix as well (``api.create``, ``api.generate``, ...)."""
 
     def __init__(self, path, prefix="gsa_"):
@@ -146,7 +155,7 @@ class Api:
         import torch  # noqa: F401
         self.lib = ctypes.CDLL(path)
         self._fns = {}
-        for header, group in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        for header, group in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPS_SIGNATURES.items()):
             for name, (res, args) in group.items():
                 try:
                     fn = getattr(self.lib, name)

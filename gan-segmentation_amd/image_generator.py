@@ -33,6 +33,12 @@ section 14): the mask returned is the rule applied to what the same call returns
 neighbour or the constant ``mask_fill`` (the rule of include_ext/gsa_components.h) -- after ``mask_morph``
 when both are on, and before anything reads the mask.  The labels and areas it works in are kept per replica, batch size and
 stream: 8 bytes per mask pixel, 256 MiB for ffhq at batch 32.  The image is untouched.
+
+``mask_ignore_band=r`` (fixed at construction; 0, the default, is off; up to 32) writes ``mask_ignore_label`` (255, the value the
+consumers ignore: ``labels="int64"`` of the training stream maps it to -1, the pair statistics count it in slot 8) into the mask of
+every fused call wherever a pixel of another value lies within r pixels -- ``mask_ops.ignore_band``, the rule of
+include_ops/gsa_boundary.h, DESIGN.md section 18: a band on both sides of every class boundary, at the output resolution, applied
+LAST, after ``mask_morph`` and the component filter, and before anything reads the mask.  The image is untouched.
 """
 import os
 
@@ -61,28 +67,34 @@ class ImageGenerator:
     mask_min_area = 0
     mask_connectivity = 8
     mask_fill = "neighbour"
+    mask_ignore_band = 0
+    mask_ignore_label = 255
 
     def __init__(self, gpu_ids, gan_dir, gan="ffhq", batch_size=4, return_latents=False, seed=0, precision="fp32",
                  truncation_psi=None, style_mix_prob=0.0, output_downscale=1, mask_morph=False, mask_min_area=0, mask_connectivity=8,
-                 mask_fill="neighbour"):
+                 mask_fill="neighbour", mask_ignore_band=0, mask_ignore_label=255):
         cfg = self._get_config(max_res_log2=_weights.GAN_MAX_RES_LOG2[gan])
         self._setup(cfg, os.path.join(gan_dir, "stylegan-%s.params" % gan), gpu_ids, batch_size, return_latents, seed, precision,
-                    truncation_psi, style_mix_prob, output_downscale, mask_morph, mask_min_area, mask_connectivity, mask_fill)
+                    truncation_psi, style_mix_prob, output_downscale, mask_morph, mask_min_area, mask_connectivity, mask_fill,
+                    mask_ignore_band, mask_ignore_label)
 
     @classmethod
     def from_params(cls, gcfg, gparams, dcfg=None, dparams=None, gpu_ids=(0,), batch_size=4,
                     return_latents=False, seed=0, precision="fp32", truncation_psi=None, style_mix_prob=0.0, output_downscale=1,
-                    mask_morph=False, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour"):
+                    mask_morph=False, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour", mask_ignore_band=0,
+                    mask_ignore_label=255):
         """Build from in-memory weights (tests, benchmarks: no pretrained files exist here)."""
         self = cls.__new__(cls)
         self._setup(dict(gcfg), gparams, gpu_ids, batch_size, return_latents, seed, precision, truncation_psi, style_mix_prob,
-                    output_downscale, mask_morph, mask_min_area, mask_connectivity, mask_fill)
+                    output_downscale, mask_morph, mask_min_area, mask_connectivity, mask_fill,
+                    mask_ignore_band, mask_ignore_label)
         if dcfg is not None:
             self.attach_decoder(dcfg, dparams)
         return self
 
     def _setup(self, cfg, gparams, gpu_ids, batch_size, return_latents, seed, precision, truncation_psi, style_mix_prob,
-               output_downscale, mask_morph, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour"):
+               output_downscale, mask_morph, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour", mask_ignore_band=0,
+               mask_ignore_label=255):
         """What both constructors do: the options, checked before any file or device is touched; one generator replica per gpu
         id, loaded from ``gparams`` (a ``.params`` path, read once, or a ``{name: array}`` dict); the seeds."""
         self.cfg = cfg
@@ -92,6 +104,8 @@ class ImageGenerator:
         self.mask_min_area = self.check_mask_min_area(mask_min_area)
         self.mask_connectivity = self.check_mask_connectivity(mask_connectivity)
         self.mask_fill = self.check_mask_fill(mask_fill)
+        self.mask_ignore_band = self.check_mask_ignore_band(mask_ignore_band)
+        self.mask_ignore_label = self.check_mask_ignore_label(mask_ignore_label)
         self.latent_size = cfg["latent_size"]
         self.return_latents = return_latents
         self.batch_size = batch_size
@@ -158,6 +172,16 @@ class ImageGenerator:
     def check_mask_fill(v):
         """What the component filter writes into a small component: "neighbour" or an int 0..255 (ValueError otherwise)."""
         return "neighbour" if _mask_ops.check_fill(v, "mask_fill") == _mask_ops.FILL_NEIGHBOUR else int(v)
+
+    @staticmethod
+    def check_mask_ignore_band(v):
+        """The radius of the ignore band as an int: 0 .. 32 pixels, 0 meaning off (ValueError otherwise)."""
+        return _mask_ops.check_band(v, "mask_ignore_band")
+
+    @staticmethod
+    def check_mask_ignore_label(v):
+        """The value the ignore band writes as an int: 0 .. 255 (ValueError otherwise)."""
+        return _mask_ops.check_label(v, "mask_ignore_label")
 
     def _get_G(self, config, device):
         return Generator(config, device=device, precision=self.precision)
@@ -355,8 +379,8 @@ class ImageGenerator:
 
     def _pair_buffers(self, r, n, out):
         """(img, raw mask, final mask) of a fused step of ``n`` samples on replica ``r``: new tensors, or the checked ``out``; the
-        step writes the raw mask, ``_finish_mask`` turns it into the final one (the same tensor without ``mask_morph`` and
-        ``mask_min_area``)."""
+        step writes the raw mask, ``_finish_mask`` turns it into the final one (the same tensor without ``mask_morph``,
+        ``mask_min_area`` and ``mask_ignore_band``)."""
         g = self._gens[r]
         dev = g._model.device
         if out is None:
@@ -376,10 +400,10 @@ class ImageGenerator:
         return img, self._finish_mask(r, raw, final)
 
     def _raw_mask(self, r, mask):
-        """Where the step of replica ``r`` writes its mask: ``mask`` itself, or with ``mask_morph`` or ``mask_min_area`` a scratch
-        tensor kept per replica, batch size and stream (calls on one stream are ordered, so they may share it) -- the same address
-        every call, so a captured graph that bakes it in stays valid whatever ``mask`` is."""
-        if not self.mask_morph and self.mask_min_area <= 1:
+        """Where the step of replica ``r`` writes its mask: ``mask`` itself, or with ``mask_morph``, ``mask_min_area`` or
+        ``mask_ignore_band`` a scratch tensor kept per replica, batch size and stream (calls on one stream are ordered, so they may
+        share it) -- the same address every call, so a captured graph that bakes it in stays valid whatever ``mask`` is."""
+        if not self.mask_morph and self.mask_min_area <= 1 and not self.mask_ignore_band:
             return mask
         return self._mask_scratch("raw", r, mask, torch.uint8)
 
@@ -393,18 +417,26 @@ class ImageGenerator:
         return t
 
     def _finish_mask(self, r, raw, final):
-        """The mask a fused call of replica ``r`` returns: the raw one passed through ``mask_morph`` and then through the component
-        filter of ``mask_min_area``, whichever are on -- eager launches behind the step on the same stream (never part of a captured
-        graph), before anything reads the mask.  The filter's labels and areas (int32 each: 8 bytes per pixel, 256 MiB for ffhq at
-        batch 32) are scratch of the same kind as the raw mask."""
+        """The mask a fused call of replica ``r`` returns: the raw one passed through ``mask_morph``, then through the component
+        filter of ``mask_min_area`` and last through the ignore band of ``mask_ignore_band``, whichever are on --
+        eager launches behind the step on the same stream (never part of a captured graph), before anything reads the mask.  The
+        filter's labels and areas (int32 each: 8 bytes per pixel, 256 MiB for ffhq at batch 32) and the masks between two stages
+        are scratch of the same kind as the raw mask."""
         if raw is final:
             return final
-        filtered = self.mask_min_area > 1
+        filtered, banded = self.mask_min_area > 1, self.mask_ignore_band > 0
+
+        def target(what, last):
+            # a stage writes the final mask if it is the last one that is on, a scratch tensor of its own otherwise
+            return final if last else self._mask_scratch(what, r, final, torch.uint8)
         if self.mask_morph:
-            raw = _mask_ops.morph_mask(raw, out=self._mask_scratch("morphed", r, final, torch.uint8) if filtered else final)
+            raw = _mask_ops.morph_mask(raw, out=target("morphed", not filtered and not banded))
         if filtered:
             scratch = (self._mask_scratch("labels", r, final, torch.int32), self._mask_scratch("areas", r, final, torch.int32))
-            _mask_ops.despeckle(raw, self.mask_min_area, self.mask_connectivity, self.mask_fill, out=final, scratch=scratch)
+            raw = _mask_ops.despeckle(raw, self.mask_min_area, self.mask_connectivity, self.mask_fill, out=target("filtered", not banded),
+                                      scratch=scratch)
+        if banded:
+            _mask_ops.ignore_band(raw, self.mask_ignore_band, self.mask_ignore_label, out=final)
         return final
 
     def _run_step(self, model, dev, n, z, nptrs, img, mask):

@@ -8,7 +8,10 @@ and ``mask_%06d.png`` (single channel, class index) into BASE_DIR/dataset/train_
 key ``OUTPUT_DOWNSCALE: f`` (1, 2, 4 or 8; default 1).  The additive key ``MASK_MORPH: true`` (default false) cleans every mask on
 the GPU with the 5x5 close + open of reference utils.morph_mask before it is written (``mask_ops.morph_mask``).  The additive keys
 ``MASK_MIN_AREA: k`` (default 0: off), ``MASK_CONNECTIVITY`` (4 or 8, default 8) and ``MASK_FILL`` ("neighbour", the default, or
-0..255) replace every connected component of fewer than k pixels, after the morphology (``mask_ops.despeckle``).  The additive key
+0..255) replace every connected component of fewer than k pixels, after the morphology (``mask_ops.despeckle``).  The additive keys
+``MASK_IGNORE_BAND: r`` (0..32 px, default 0: off) and ``MASK_IGNORE_LABEL`` (0..255, default 255) then write the label into every
+pixel within r pixels of a pixel of another class, on both sides of every class boundary (``mask_ops.ignore_band``): the stored
+``mask_*.png`` holds 255 there, the value the reference's dataset readers map to -1.  The additive key
 ``PAIR_STATS: true`` (default false) adds one ``pair_stats_<first>_<last + 1>.npz`` per rank with the per-sample statistics of the
 written pairs (``pair_stats.pair_stats``); ``python -m gan_segmentation_amd.pair_stats DIR`` merges them into a report.
 With torchrun (one process per GPU) the sample indices are sharded across ranks and every rank
@@ -81,6 +84,9 @@ def generate(cfg, limit=None, workers=None):
     mask_min_area = ImageGenerator.check_mask_min_area(cfg.get("MASK_MIN_AREA", 0))
     mask_connectivity = ImageGenerator.check_mask_connectivity(cfg.get("MASK_CONNECTIVITY", 8))
     mask_fill = ImageGenerator.check_mask_fill(cfg.get("MASK_FILL", "neighbour"))
+    # additive keys, checked here as well: the ignore band around class boundaries (off by default), applied last
+    mask_ignore_band = ImageGenerator.check_mask_ignore_band(cfg.get("MASK_IGNORE_BAND", 0))
+    mask_ignore_label = ImageGenerator.check_mask_ignore_label(cfg.get("MASK_IGNORE_LABEL", 255))
     stats = check_pair_stats(cfg.get("PAIR_STATS", False))    # additive key, checked here as well: every rank writes its own shard file
 
     solver = SegSolver(GAN_MAX_RES_LOG2[gan], os.path.join(root_dir, "data"), os.path.join(root_dir, "checkpoints"),
@@ -90,7 +96,8 @@ def generate(cfg, limit=None, workers=None):
         return -1
     netG = ImageGenerator(gpu_ids=gan_ids, gan_dir=gan_dir, gan=gan, batch_size=batch, precision=precision,
                           truncation_psi=truncation_psi, style_mix_prob=style_mix_prob, output_downscale=downscale,
-                          mask_morph=mask_morph, mask_min_area=mask_min_area, mask_connectivity=mask_connectivity, mask_fill=mask_fill)
+                          mask_morph=mask_morph, mask_min_area=mask_min_area, mask_connectivity=mask_connectivity, mask_fill=mask_fill,
+                          mask_ignore_band=mask_ignore_band, mask_ignore_label=mask_ignore_label)
     netG.attach_decoder(solver.cfg, solver.net)
     dst_dir = os.path.join(root_dir, "dataset", "train_generated")
     os.makedirs(dst_dir, exist_ok=True)

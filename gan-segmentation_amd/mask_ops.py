@@ -8,7 +8,13 @@ Also the binding of the mask components (include_ext/gsa_components.h, csrc/gsa_
 reference does not have: ``components(mask)`` labels the connected components of equal value and gives their areas,
 ``despeckle(mask, min_area)`` replaces every component smaller than ``min_area`` pixels -- a clean-up with an area threshold where
 the morphology has a window size -- and can return per-sample component counts; ``ImageGenerator(..., mask_min_area=k)`` applies it
-to the mask of every fused call, after ``mask_morph``."""
+to the mask of every fused call, after ``mask_morph``.
+
+And the binding of the boundary distance (include_ops/gsa_boundary.h, csrc/gsa_boundary.hip), which the
+reference does not have either: ``boundary_distance(mask)`` gives every pixel's squared Euclidean distance to the nearest pixel of
+another value, up to a radius; ``ignore_band(mask, radius)`` writes a label (255, the value the consumers ignore) wherever that
+distance is at most ``radius``^2 -- VOC's void border, on both sides of every class boundary; ``ImageGenerator(...,
+mask_ignore_band=r)`` applies it to the mask of every fused call, last."""
 import numpy as np
 import torch
 
@@ -27,6 +33,11 @@ COMP_ROW = 20
 FILL_NEIGHBOUR = -1
 CONNECTIVITIES = (4, 8)
 MAX_AREA = 2 ** 31 - 1
+
+# include_ops/gsa_boundary.h
+BOUNDARY_FAR = 32767        # dist2 of a pixel with no other value within the radius
+BOUNDARY_MAX_RADIUS = 32
+
 
 def _check(t, what):
     if not is_device_tensor(t, torch.uint8, dims=(2, 3)):
@@ -152,3 +163,68 @@ def despeckle(mask, min_area, connectivity=8, fill="neighbour", out=None, return
     if return_stats:
         return out, (rows[0] if mask.dim() == 2 else rows)
     return out
+
+
+def check_band(v, what="radius"):
+    """A band radius in pixels as an int: 0 .. 32, 0 meaning off (only the ``ImageGenerator`` keyword and the config key take it;
+    the functions below want 1 .. 32).  ValueError otherwise; a bool is not a number here."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= BOUNDARY_MAX_RADIUS:
+        raise ValueError("%s must be an int in 0..%d, got %r" % (what, BOUNDARY_MAX_RADIUS, v))
+    return int(v)
+
+
+def check_label(v, what="label"):
+    """The value the band writes as an int: 0 .. 255.  ValueError otherwise."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 255:
+        raise ValueError("%s must be an int in 0..255, got %r" % (what, v))
+    return int(v)
+
+
+def _radius(v, what):
+    r = check_band(v, what)
+    if r == 0:
+        raise ValueError("%s must be an int in 1..%d, got %r" % (what, BOUNDARY_MAX_RADIUS, v))
+    return r
+
+
+def _other_tensor(out, what, dtype, mask):
+    """``out`` checked as the result ``what`` of ``mask``'s shape: contiguous, of ``dtype``, on the same device, not overlapping it."""
+    if not is_device_tensor(out, dtype, shape=mask.shape, device=mask.device):
+        raise ValueError("%s must be a contiguous %s tensor %s on %s" % (what, str(dtype).replace("torch.", ""), tuple(mask.shape), mask.device))
+    a, b, size, other = mask.data_ptr(), out.data_ptr(), mask.numel(), out.numel() * out.element_size()
+    if out is mask or (size and a < b + other and b < a + size):
+        raise ValueError("%s must not be, or overlap, the input mask" % what)
+    return out
+
+
+def boundary_distance(mask, max_radius=BOUNDARY_MAX_RADIUS, out=None):
+    """mask (H, W) or (n, H, W) contiguous uint8 CUDA tensor -> an int16 tensor of the same shape (new, or ``out``): every pixel's
+    squared Euclidean distance to the nearest pixel of its plane with another raw value where that is at most ``max_radius``^2
+    (``max_radius`` 1..32), and ``BOUNDARY_FAR`` (32767) elsewhere.  The outside of the image is not another value: an image edge
+    makes no boundary, and a constant plane is FAR everywhere (the rule of include_ops/gsa_boundary.h).  What boundary-weighted
+    losses, one-sided bands and trimaps are built from.  Enqueued on the current stream of ``mask``'s device; the input is not
+    written.  ValueError on anything else; no CPU fallback."""
+    n, H, W = _plane_shape(mask, "boundary_distance")
+    radius = _radius(max_radius, "max_radius")
+    dist2 = torch.empty(mask.shape, dtype=torch.int16, device=mask.device) if out is None else _other_tensor(out, "out", torch.int16, mask)
+    if n:
+        launch("gsa_mask_boundary", mask.device, n, H, W, radius, 0, mask.data_ptr(), dist2.data_ptr(), None)
+    return dist2
+
+
+def ignore_band(mask, radius, label=255, out=None, return_distance=False):
+    """mask (H, W) or (n, H, W) contiguous uint8 CUDA tensor -> a tensor of the same shape (new, or ``out``, which must not overlap
+    ``mask``) that holds ``label`` (0..255) wherever a pixel of another value lies within ``radius`` (1..32) pixels, Euclidean,
+    ``radius``^2 inclusive, and the input's value elsewhere: a band on both sides of every class boundary.  One pass on the input's
+    values; a pixel that already holds ``label`` is a value like any other; image edges make no band.
+    ``return_distance=True`` returns ``(out, dist2)`` with ``dist2`` as ``boundary_distance(mask, radius)`` gives it, from the same
+    launch.  Enqueued on the current stream of ``mask``'s device; the input is not written.  ValueError on anything else; no CPU
+    fallback."""
+    n, H, W = _plane_shape(mask, "ignore_band")
+    radius, label = _radius(radius, "radius"), check_label(label)
+    out = torch.empty_like(mask) if out is None else _other_tensor(out, "out", torch.uint8, mask)
+    dist2 = torch.empty(mask.shape, dtype=torch.int16, device=mask.device) if return_distance else None
+    if n:
+        launch("gsa_mask_boundary", mask.device, n, H, W, radius, label, mask.data_ptr(), dist2.data_ptr() if return_distance else None,
+               out.data_ptr())
+    return (out, dist2) if return_distance else out

@@ -1,0 +1,384 @@
+"""The mask boundary distance and the ignore band without a GPU (include_ops/gsa_boundary.h; mask_ops.boundary_distance / ignore_band;
+ImageGenerator(mask_ignore_band=...); the MASK_IGNORE_BAND and MASK_IGNORE_LABEL keys).
+
+``rule_boundary(m, R)`` is the canonical rule in its separable form, in numpy: the vertical distance h to the nearest other value of
+the column, then the minimum over |dx| <= R of dx^2 + (other value ? 0 : h^2).  ``rule_band(m, R, label)`` is the band.  The rule is
+PINNED here, with zero differences allowed, against a brute-force search of the (2R+1)^2 window and, where scipy imports, against
+``scipy.ndimage.distance_transform_edt`` taken per value, squared and rounded.  The GPU tests (tests/test_gpu_boundary.py) hold the
+kernel to this rule over every pixel.  Also here: hand cases, the table of include_ops/ against the headers' text and the library's
+exports, the entry's argument checks, and the validation of the keywords and the keys."""
+import os
+
+import numpy as np
+import pytest
+
+from tests.test_downscale_host import _config
+from tests.test_mask_morph_host import _blur
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+FAR = 32767
+MAX_RADIUS = 32
+
+
+# -- the rule ------------------------------------------------------------------------------------------------------------------
+def _plane_boundary(m, R):
+    H, W = m.shape
+    big = 1 << 20
+    # h: vertical distance to the nearest pixel of the same column with another value; beyond R: none
+    h = np.full((H, W), big, np.int64)
+    for d in range(R, 0, -1):
+        hit = np.zeros((H, W), bool)
+        hit[d:] |= m[d:] != m[:-d]
+        hit[:-d] |= m[:-d] != m[d:]
+        h[hit] = d
+    D = np.where(h < big, h * h, big)
+    for dx in range(1, R + 1):
+        if dx >= W:
+            break
+        # the tap at x + dx, for the pixels that have one inside the image; then the tap at x - dx
+        g = np.where(m[:, dx:] != m[:, :-dx], 0, np.where(h[:, dx:] < big, h[:, dx:] ** 2, big))
+        D[:, :-dx] = np.minimum(D[:, :-dx], dx * dx + g)
+        g = np.where(m[:, :-dx] != m[:, dx:], 0, np.where(h[:, :-dx] < big, h[:, :-dx] ** 2, big))
+        D[:, dx:] = np.minimum(D[:, dx:], dx * dx + g)
+    return np.where(D <= R * R, D, FAR).astype(np.int16)
+
+
+def rule_boundary(m, R=MAX_RADIUS):
+    """(H, W) or (n, H, W) u8 -> int16 of the same shape: the squared distance to the nearest pixel of the plane with another raw
+    value where that is <= R*R, FAR elsewhere; every image of a batch on its own; the outside of the image is no value."""
+    m = np.asarray(m)
+    assert m.dtype == np.uint8 and m.ndim in (2, 3) and 1 <= R <= MAX_RADIUS
+    if m.ndim == 2:
+        return _plane_boundary(m, R)
+    return np.stack([_plane_boundary(p, R) for p in m]) if len(m) else np.zeros(m.shape, np.int16)
+
+
+def rule_band(m, R, label=255, dist2=None):
+    """out of the header's text: label where D <= R*R, the input elsewhere."""
+    m = np.asarray(m)
+    assert 0 <= label <= 255
+    d = rule_boundary(m, R) if dist2 is None else dist2
+    return np.where(d != FAR, np.uint8(label), m).astype(np.uint8)
+
+
+def brute_boundary(m, R):
+    """The definition, pixel by pixel over the clipped (2R+1)^2 window."""
+    H, W = m.shape
+    out = np.full((H, W), FAR, np.int64)
+    for y in range(H):
+        for x in range(W):
+            ya, yb, xa, xb = max(0, y - R), min(H, y + R + 1), max(0, x - R), min(W, x + R + 1)
+            yy, xx = np.nonzero(m[ya:yb, xa:xb] != m[y, x])
+            if len(yy):
+                d = int(((yy + ya - y) ** 2 + (xx + xa - x) ** 2).min())
+                if d <= R * R:
+                    out[y, x] = d
+    return out.astype(np.int16)
+
+
+def scipy_boundary(m, R):
+    """The same by scipy's exact Euclidean distance transform, value by value."""
+    from scipy import ndimage as ndi
+    values = np.unique(m)
+    if len(values) == 1:
+        return np.full(m.shape, FAR, np.int16)
+    D2 = np.zeros(m.shape, np.int64)
+    for v in values:
+        d = ndi.distance_transform_edt(m == v)      # of the v-pixels, to the nearest pixel that is not v
+        D2 = np.where(m == v, np.rint(d * d).astype(np.int64), D2)
+    return np.where(D2 <= R * R, D2, FAR).astype(np.int16)
+
+
+# -- the inputs ----------------------------------------------------------------------------------------------------------------
+def class_blobs(seed, shape, classes=3, sigma=2.0, with255=False):
+    """Smooth regions of ``classes`` values: the argmax of blurred noise fields, per plane.  ``with255``: the last class is stored
+    as 255, a value like any other."""
+    rng = np.random.default_rng([seed, classes])
+    shape = tuple(shape)
+    f = np.stack([_blur(rng.standard_normal(shape), sigma) for _ in range(classes)])
+    m = f.argmax(0).astype(np.uint8)
+    if with255:
+        m[m == classes - 1] = 255
+    return m
+
+
+def has_both(d):
+    """Whether an expected distance map holds FAR and non-FAR pixels: a case where it does not proves little."""
+    return bool((d == FAR).any() and (d != FAR).any())
+
+
+def test_the_inputs_have_the_classes_they_name():
+    for classes in (2, 3, 8):
+        m = class_blobs(1, (64, 80), classes)
+        assert len(np.unique(m)) == classes and m.dtype == np.uint8
+    m = class_blobs(1, (2, 40, 40), 3, with255=True)
+    assert set(np.unique(m)) == {0, 1, 255} and not np.array_equal(m[0], m[1])
+
+
+# -- the pins ------------------------------------------------------------------------------------------------------------------
+PINS = [((16, 16), 2, 1), ((37, 53), 3, 5), ((33, 130), 4, 32)]
+
+
+def _same(got, want, what):
+    assert got.shape == want.shape and got.dtype == want.dtype == np.int16, what
+    assert int((got != want).sum()) == 0, what
+
+
+@pytest.mark.parametrize("shape,classes,R", PINS)
+def test_rule_equals_the_brute_force_search(shape, classes, R):
+    m = class_blobs(sum(shape), shape, classes)
+    want = brute_boundary(m, R)
+    assert has_both(want) or (R >= shape[0] - 1 and (want != FAR).all())    # 33 rows at R = 32: every pixel is in some band
+    _same(rule_boundary(m, R), want, (shape, classes, R))
+
+
+def test_rule_equals_the_brute_force_search_on_noise_and_at_every_small_radius():
+    rng = np.random.default_rng(7)
+    m = (rng.random((19, 23)) < 0.08).astype(np.uint8) * 255
+    m[3, 4:9] = 7
+    for R in (1, 2, 3, 4, 5, 8):
+        _same(rule_boundary(m, R), brute_boundary(m, R), R)
+
+
+def test_rule_equals_scipys_distance_transform():
+    pytest.importorskip("scipy.ndimage")
+    for shape, classes, R in PINS + [((64, 64), 2, 32), ((70, 45), 8, 9)]:
+        m = class_blobs(sum(shape), shape, classes)
+        _same(rule_boundary(m, R), scipy_boundary(m, R), (shape, classes, R))
+    m = class_blobs(5, (1024, 1024), 2, sigma=12.0)
+    want = scipy_boundary(m, 32)
+    assert has_both(want)
+    _same(rule_boundary(m, 32), want, "1024 x 1024")
+    _same(rule_boundary(np.full((9, 9), 4, np.uint8), 3), scipy_boundary(np.full((9, 9), 4, np.uint8), 3), "constant")
+
+
+# -- hand cases ----------------------------------------------------------------------------------------------------------------
+def test_a_constant_plane_is_far_and_the_band_changes_nothing():
+    for value in (0, 3, 255):
+        m = np.full((12, 17), value, np.uint8)
+        for R in (1, 5, 32):
+            assert (rule_boundary(m, R) == FAR).all()
+            assert np.array_equal(rule_band(m, R, 9), m)
+
+
+def test_a_checkerboard_is_all_ones():
+    m = ((np.arange(10)[:, None] + np.arange(13)[None, :]) & 1).astype(np.uint8)
+    for R in (1, 4, 32):
+        assert (rule_boundary(m, R) == 1).all()
+        assert (rule_band(m, R) == 255).all()
+
+
+def test_a_single_odd_pixel():
+    m = np.zeros((9, 9), np.uint8)
+    m[4, 4] = 1
+    yy, xx = np.mgrid[:9, :9]
+    disc = (yy - 4) ** 2 + (xx - 4) ** 2
+    for R in (1, 2, 3, 4):
+        d = rule_boundary(m, R)
+        assert d[4, 4] == 1, "its own distance: to its 4-neighbours"
+        want = np.where(disc <= R * R, disc, FAR)
+        want[4, 4] = 1
+        assert np.array_equal(d, want), "its neighbours' distances are the disc"
+        band = rule_band(m, R)
+        assert int((band == 255).sum()) == int((disc <= R * R).sum()) and band[0, 0] == 0
+
+
+def test_a_vertical_edge_gives_columns_of_squares_on_both_sides():
+    m = np.zeros((7, 20), np.uint8)
+    m[:, 10:] = 2
+    d = rule_boundary(m, 4)
+    assert d[3].tolist() == [FAR] * 6 + [16, 9, 4, 1, 1, 4, 9, 16] + [FAR] * 6
+    assert (d == d[3]).all(), "every row alike: the image edges above and below add nothing"
+    assert rule_band(m, 2, 255)[0].tolist() == [0] * 8 + [255] * 4 + [2] * 8
+    d = rule_boundary(m.T.copy(), 4)
+    assert d[:, 2].tolist() == [FAR] * 6 + [16, 9, 4, 1, 1, 4, 9, 16] + [FAR] * 6
+
+
+def test_the_radius_is_inclusive():
+    m = np.zeros((3, 12), np.uint8)
+    m[:, 0] = 1
+    for R in (1, 3, 5):
+        d = rule_boundary(m, R)
+        assert d[1, R] == R * R and d[1, R + 1] == FAR
+        assert rule_band(m, R)[1, R] == 255 and rule_band(m, R)[1, R + 1] == 0
+    m = np.zeros((9, 9), np.uint8)                  # 3-4-5: a diagonal neighbour at distance^2 exactly 25
+    m[0, 0] = 1
+    assert rule_boundary(m, 5)[3, 4] == 25 and rule_boundary(m, 5)[4, 4] == FAR and rule_boundary(m, 4)[3, 4] == FAR
+
+
+def test_image_edges_make_no_band():
+    m = np.zeros((20, 20), np.uint8)
+    m[8:12, 8:12] = 1
+    d = rule_boundary(m, 3)
+    for edge in (d[0], d[-1], d[:, 0], d[:, -1]):
+        assert (edge == FAR).all()
+    m = np.zeros((6, 6), np.uint8)
+    m[0, 0] = 5                                     # a corner pixel: the band is the quarter disc inside the image
+    d = rule_boundary(m, 2)
+    assert d[0, 0] == 1 and d[:3, :3].tolist() == [[1, 1, 4], [1, 2, FAR], [4, FAR, FAR]] and (d[3:] == FAR).all()
+
+
+def test_value_255_is_a_value_like_any_other():
+    m = np.full((5, 9), 255, np.uint8)
+    m[:, 5:] = 0
+    d = rule_boundary(m, 2)
+    assert d[2].tolist() == [FAR, FAR, FAR, 4, 1, 1, 4, FAR, FAR]
+    # the band's label among the input's values: no special case, and ONE pass -- what the band writes does not feed back
+    assert rule_band(m, 1, 255)[2].tolist() == [255, 255, 255, 255, 255, 255, 0, 0, 0]
+    assert rule_band(m, 1, 0)[2].tolist() == [255, 255, 255, 255, 0, 0, 0, 0, 0]
+    assert rule_band(m, 1, 7)[2].tolist() == [255, 255, 255, 255, 7, 7, 0, 0, 0]
+
+
+def test_every_image_of_a_batch_is_a_plane_of_its_own():
+    batch = np.stack([np.ones((16, 16), np.uint8), class_blobs(5, (16, 16), 2), np.full((16, 16), 2, np.uint8)])
+    d = rule_boundary(batch, 6)
+    assert d.shape == (3, 16, 16) and (d[0] == FAR).all() and (d[2] == FAR).all() and has_both(d[1])
+    for i in range(3):
+        assert np.array_equal(d[i], rule_boundary(batch[i], 6))
+    assert rule_boundary(batch[:0], 6).shape == (0, 16, 16) and rule_boundary(batch[:0], 6).dtype == np.int16
+    assert rule_band(batch[:0], 6).shape == (0, 16, 16) and rule_band(batch[:0], 6).dtype == np.uint8
+
+
+# -- the C ABI -----------------------------------------------------------------------------------------------------------------
+def test_ops_table_matches_the_headers(hip_library):
+    """The directory listing against the table's keys (no literal list: the next header needs no fourth directory); every header's
+    declarations against its group and the library's exports, kind by kind; the macros against the Python constants."""
+    import ctypes
+    from gan_segmentation_amd import _lib, mask_ops
+    from tests.common import ctypes_kind, header_declarations
+    assert sorted(os.listdir(os.path.join(ROOT, "include_ops"))) == sorted(_lib.OPS_SIGNATURES)
+    assert "gsa_boundary.h" in _lib.OPS_SIGNATURES
+    lib = ctypes.CDLL(hip_library)
+    others = {n for table in (_lib.SIGNATURES, _lib.EXT_SIGNATURES) for g in table.values() for n in g}
+    for header, table in _lib.OPS_SIGNATURES.items():
+        text, declared = header_declarations("../include_ops/" + header)
+        assert set(declared) == set(table) and table, header
+        for name, (res, args) in table.items():
+            assert hasattr(lib, name), "%s is not exported" % name
+            assert (ctypes_kind(res), [ctypes_kind(a) for a in args]) == declared[name], name
+            assert name not in others, "%s is bound twice" % name
+            assert _lib.load_library().fn(name) is not None
+    text, declared = header_declarations("../include_ops/gsa_boundary.h")
+    assert set(declared) == {"gsa_mask_boundary"}
+    for macro, value in (("FAR", mask_ops.BOUNDARY_FAR), ("MAX_RADIUS", mask_ops.BOUNDARY_MAX_RADIUS)):
+        assert "#define GSA_BOUNDARY_%s %d " % (macro, value) in text.replace("\n", " \n"), macro
+    assert (mask_ops.BOUNDARY_FAR, mask_ops.BOUNDARY_MAX_RADIUS) == (FAR, MAX_RADIUS)
+
+
+def test_entry_rejects_bad_arguments_before_touching_the_gpu(hip_library):
+    """Argument validation of gsa_mask_boundary happens on the host (no HIP call precedes it): fake pointers, no device."""
+    from gan_segmentation_amd._lib import load_library
+    fn = load_library().fn("gsa_mask_boundary")
+    good = dict(n=2, H=32, W=48, radius=3, label=255, mask=1 << 20, dist2=2 << 20, out=4 << 20)
+    size = 2 * 32 * 48
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return fn(None, a["n"], a["H"], a["W"], a["radius"], a["label"], a["mask"], a["dist2"], a["out"])
+
+    for bad in (dict(n=-1), dict(H=0), dict(W=0), dict(H=65536), dict(W=65536), dict(H=65535, W=65535), dict(H=32768, W=65535),
+                dict(radius=0), dict(radius=33), dict(radius=-1), dict(label=-1), dict(label=256), dict(label=256, out=None),
+                dict(mask=None), dict(dist2=None, out=None), dict(out=1 << 20), dict(out=(1 << 20) + size - 1),
+                dict(mask=(4 << 20) + 1), dict(out=(1 << 20) - size + 1), dict(dist2=(2 << 20) + 1), dict(dist2=(2 << 20) + 1, out=None),
+                dict(dist2=1 << 20), dict(dist2=(1 << 20) + size - 2), dict(dist2=(4 << 20) - 2 * size + 2),
+                dict(n=1 << 14, H=2048, W=2048, mask=1 << 40, dist2=None, out=1 << 50)):
+        assert call(**bad) == -1, bad
+    assert call(n=0) == 0 and call(n=0, mask=None, dist2=None, out=None) == 0
+    assert call(n=0, radius=33) == -1 and call(n=0, label=256) == -1 and call(n=0, H=0) == -1
+
+
+def test_wrappers_check_their_arguments_before_any_gpu_work():
+    import torch
+    from gan_segmentation_amd import mask_ops
+    for bad in (torch.zeros((4, 4), dtype=torch.uint8), torch.zeros((1, 4, 4), dtype=torch.float32), np.zeros((4, 4), np.uint8), None):
+        with pytest.raises(ValueError, match="mask"):
+            mask_ops.boundary_distance(bad)
+        with pytest.raises(ValueError, match="mask"):
+            mask_ops.ignore_band(bad, 2)
+    assert mask_ops.check_band(0) == 0 and mask_ops.check_band(np.int64(32)) == 32 and type(mask_ops.check_band(np.int64(2))) is int
+    assert mask_ops.check_label(0) == 0 and mask_ops.check_label(np.uint8(255)) == 255 and type(mask_ops.check_label(np.uint8(1))) is int
+    for fn, values in ((mask_ops.check_band, (-1, 33, 2.0, "2", None, True, False)), (mask_ops.check_label, (-1, 256, 255.0, "255", None, True))):
+        for v in values:
+            with pytest.raises(ValueError, match="radius" if fn is mask_ops.check_band else "label"):
+                fn(v)
+    with pytest.raises(ValueError, match="mask_ignore_band"):
+        mask_ops.check_band(40, "mask_ignore_band")
+
+
+# -- the keywords and the keys -------------------------------------------------------------------------------------------------
+BAD_KEYWORDS = [("mask_ignore_band", -1), ("mask_ignore_band", 33), ("mask_ignore_band", 2.0), ("mask_ignore_band", "2"),
+                ("mask_ignore_band", True), ("mask_ignore_band", None), ("mask_ignore_label", -1), ("mask_ignore_label", 256),
+                ("mask_ignore_label", 255.0), ("mask_ignore_label", "255"), ("mask_ignore_label", True), ("mask_ignore_label", None)]
+
+
+@pytest.mark.parametrize("name,value", BAD_KEYWORDS)
+def test_keywords_reject_bad_values_before_any_device_work(name, value):
+    from gan_segmentation_amd import weights as W
+    from gan_segmentation_amd.image_generator import ImageGenerator
+    with pytest.raises(ValueError, match=name):
+        getattr(ImageGenerator, "check_" + name)(value)
+    with pytest.raises(ValueError, match=name):
+        ImageGenerator.from_params(W.reduced_generator_config(7), {}, gpu_ids=[0], **{name: value})
+
+
+def test_keywords_accept_and_default_to_off():
+    import inspect
+    from gan_segmentation_amd.image_generator import ImageGenerator
+    assert ImageGenerator.check_mask_ignore_band(0) == 0 and ImageGenerator.check_mask_ignore_band(np.int64(32)) == 32
+    assert type(ImageGenerator.check_mask_ignore_band(np.int64(3))) is int
+    assert ImageGenerator.check_mask_ignore_label(0) == 0 and ImageGenerator.check_mask_ignore_label(255) == 255
+    assert (ImageGenerator.mask_ignore_band, ImageGenerator.mask_ignore_label) == (0, 255)
+    for fn in (ImageGenerator.__init__, ImageGenerator.from_params, ImageGenerator._setup):
+        p = inspect.signature(fn).parameters
+        assert (p["mask_ignore_band"].default, p["mask_ignore_label"].default) == (0, 255)
+        assert list(p)[-2:] == ["mask_ignore_band", "mask_ignore_label"], "the new parameters go last"
+
+
+class _ModelLoaded(Exception):
+    pass
+
+
+@pytest.fixture
+def no_models(monkeypatch):
+    """`main.py generate` stops where it would load the first model."""
+    from gan_segmentation_amd import seg_solver
+
+    def refuse(*args, **kwargs):
+        raise _ModelLoaded()
+    monkeypatch.setattr(seg_solver, "SegSolver", refuse)
+
+
+@pytest.mark.parametrize("key,value,name", [("MASK_IGNORE_BAND", -2, "mask_ignore_band"), ("MASK_IGNORE_BAND", 33, "mask_ignore_band"),
+                                            ("MASK_IGNORE_BAND", "wide", "mask_ignore_band"), ("MASK_IGNORE_BAND", 1.5, "mask_ignore_band"),
+                                            ("MASK_IGNORE_BAND", True, "mask_ignore_band"), ("MASK_IGNORE_LABEL", 300, "mask_ignore_label"),
+                                            ("MASK_IGNORE_LABEL", "void", "mask_ignore_label"), ("MASK_IGNORE_LABEL", -1, "mask_ignore_label")])
+def test_cli_rejects_a_bad_key_before_loading_a_model(tmp_path, no_models, key, value, name):
+    from gan_segmentation_amd import main as cli
+    with pytest.raises(ValueError, match=name):
+        cli.main(["generate", "--config", _config(tmp_path, **{key: value})])
+
+
+def test_cli_accepts_the_keys_and_their_defaults(tmp_path, no_models):
+    from gan_segmentation_amd import main as cli
+    for keys in ({}, {"MASK_IGNORE_BAND": 0}, {"MASK_IGNORE_BAND": 2}, {"MASK_IGNORE_BAND": 32, "MASK_IGNORE_LABEL": 0},
+                 {"MASK_IGNORE_BAND": 3, "MASK_IGNORE_LABEL": 255, "MASK_MORPH": True, "MASK_MIN_AREA": 64}):
+        with pytest.raises(_ModelLoaded):
+            cli.main(["generate", "--config", _config(tmp_path, **keys)])
+    for key in ("MASK_IGNORE_BAND", "MASK_IGNORE_LABEL"):
+        assert key in cli.__doc__
+
+
+# -- the PNG path --------------------------------------------------------------------------------------------------------------
+def test_a_banded_mask_survives_the_host_png_path(tmp_path):
+    """A mask that holds 0, 1 and the band's 255 goes through the dataset writer's host encoder and reads back equal with PIL."""
+    from PIL import Image
+    from gan_segmentation_amd import dataset_writer
+    m = class_blobs(3, (48, 40), 2)
+    banded = rule_band(m, 2, 255)
+    assert set(np.unique(banded)) == {0, 1, 255}
+    img = np.zeros(banded.shape + (3,), np.uint8)
+    dataset_writer.write_pair(str(tmp_path), 0, img, banded)
+    back = np.asarray(Image.open(tmp_path / "mask_000000.png"))
+    assert back.dtype == np.uint8 and back.shape == banded.shape and np.array_equal(back, banded)
+    assert int((back == 255).sum()) == int((rule_boundary(m, 2) != FAR).sum()) > 0
