@@ -119,21 +119,9 @@ SIGNATURES = {
     "gsa_stats.h": {
         "gsa_pair_stats": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     },
-}
-
-# The headers under include_ext/, in the same form: the set of headers under include/ and the keys of SIGNATURES are pinned by
-# tests/test_abi_and_host.py, so an ABI added since lives beside them.  tests/test_components_host.py checks this table against the
-# header's text.
-EXT_SIGNATURES = {
     "gsa_components.h": {
         "gsa_mask_components": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     },
-}
-
-# The headers under include_ops/, in the same form.  The file list of include_ext/ and the keys of EXT_SIGNATURES are pinned as well
-# (tests/test_components_host.py); tests/test_boundary_host.py checks the listing of include_ops/ against the keys of THIS table and
-# every header's text against its group, so the next header needs a file and a group here, no fourth directory.
-OPS_SIGNATURES = {
     "gsa_boundary.h": {
         "gsa_mask_boundary": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     },
@@ -141,8 +129,8 @@ OPS_SIGNATURES = {
 
 
 class Api:
-    """Function table of one shared library: every entry of ``SIGNATURES``, ``EXT_SIGNATURES`` and ``OPS_SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full
-    name; the entries of include/gsa.h are attributes without the prefix as well (``api.create``, ``api.generate``, ...)."""
+    """Function table of one shared library: every entry of ``SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full name;
+    the entries of include/gsa.h are attributes without the prefix as well (``api.create``, ``api.generate``, ...)."""
 
     def __init__(self, path, prefix="gsa_"):
         if not os.path.exists(path):
@@ -155,7 +143,7 @@ class Api:
         import torch  # noqa: F401
         self.lib = ctypes.CDLL(path)
         self._fns = {}
-        for header, group in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPS_SIGNATURES.items()):
+        for header, group in SIGNATURES.items():
             for name, (res, args) in group.items():
                 try:
                     fn = getattr(self.lib, name)

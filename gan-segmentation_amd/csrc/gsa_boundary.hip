@@ -1,4 +1,4 @@
-// gsa_boundary.hip -- the mask boundary distance's one kernel (include_ops/gsa_boundary.h): for every pixel
+// gsa_boundary.hip -- the mask boundary distance's one kernel (include/gsa_boundary.h): for every pixel
 // of every (H, W) u8 plane the squared Euclidean distance to the nearest pixel of another value, up to a radius R <= 32, and the
 // mask with `label` wherever that distance is at most R*R.
 //
@@ -28,7 +28,7 @@
 #include <cstdint>
 
 #include "../../include/gsa.h"
-#include "../../include_ops/gsa_boundary.h"
+#include "../../include/gsa_boundary.h"
 
 namespace {
 

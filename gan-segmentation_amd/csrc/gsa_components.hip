@@ -1,4 +1,4 @@
-// gsa_components.hip -- the mask components' kernels (include_ext/gsa_components.h): labels (smallest raster
+// gsa_components.hip -- the mask components' kernels (include/gsa_components.h): labels (smallest raster
 // index of the component), areas, the area-threshold filter and the per-sample summary rows of every (H, W) u8 plane.
 //
 // A data-dependent union-find, unlike the fixed-shape stencils and reductions beside it.  ONE invariant carries every phase:
@@ -34,7 +34,7 @@
 #include <cstdint>
 
 #include "../../include/gsa.h"
-#include "../../include_ext/gsa_components.h"
+#include "../../include/gsa_components.h"
 
 namespace {
 

@@ -30,14 +30,14 @@ section 14): the mask returned is the rule applied to what the same call returns
 
 ``mask_min_area=k`` (fixed at construction; 0, the default, and 1 are off) passes the mask of every fused call through
 ``mask_ops.despeckle``: every connected component of fewer than k pixels (``mask_connectivity`` 4 or 8) takes the value of its
-neighbour or the constant ``mask_fill`` (the rule of include_ext/gsa_components.h) -- after ``mask_morph``
+neighbour or the constant ``mask_fill`` (the rule of include/gsa_components.h) -- after ``mask_morph``
 when both are on, and before anything reads the mask.  The labels and areas it works in are kept per replica, batch size and
 stream: 8 bytes per mask pixel, 256 MiB for ffhq at batch 32.  The image is untouched.
 
 ``mask_ignore_band=r`` (fixed at construction; 0, the default, is off; up to 32) writes ``mask_ignore_label`` (255, the value the
 consumers ignore: ``labels="int64"`` of the training stream maps it to -1, the pair statistics count it in slot 8) into the mask of
 every fused call wherever a pixel of another value lies within r pixels -- ``mask_ops.ignore_band``, the rule of
-include_ops/gsa_boundary.h, DESIGN.md section 18: a band on both sides of every class boundary, at the output resolution, applied
+include/gsa_boundary.h, DESIGN.md section 18: a band on both sides of every class boundary, at the output resolution, applied
 LAST, after ``mask_morph`` and the component filter, and before anything reads the mask.  The image is untouched.
 """
 import os

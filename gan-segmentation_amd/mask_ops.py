@@ -4,13 +4,13 @@ counterpart of reference utils.morph_mask (utils.py:105-109): a 5x5 close follow
 ``morph_mask(mask)`` enqueues one kernel on the current stream of ``mask``'s device and returns the cleaned mask;
 ``ImageGenerator(..., mask_morph=True)`` applies it to the mask of every fused call.  No CPU fallback.
 
-Also the binding of the mask components (include_ext/gsa_components.h, csrc/gsa_components.hip), which the
+Also the binding of the mask components (include/gsa_components.h, csrc/gsa_components.hip), which the
 reference does not have: ``components(mask)`` labels the connected components of equal value and gives their areas,
 ``despeckle(mask, min_area)`` replaces every component smaller than ``min_area`` pixels -- a clean-up with an area threshold where
 the morphology has a window size -- and can return per-sample component counts; ``ImageGenerator(..., mask_min_area=k)`` applies it
 to the mask of every fused call, after ``mask_morph``.
 
-And the binding of the boundary distance (include_ops/gsa_boundary.h, csrc/gsa_boundary.hip), which the
+And the binding of the boundary distance (include/gsa_boundary.h, csrc/gsa_boundary.hip), which the
 reference does not have either: ``boundary_distance(mask)`` gives every pixel's squared Euclidean distance to the nearest pixel of
 another value, up to a radius; ``ignore_band(mask, radius)`` writes a label (255, the value the consumers ignore) wherever that
 distance is at most ``radius``^2 -- VOC's void border, on both sides of every class boundary; ``ImageGenerator(...,
@@ -22,7 +22,7 @@ from ._runtime import is_device_tensor, launch
 
 MAX_EXTENT = 65535
 
-# The summary row of ``despeckle(..., return_stats=True)``: COMP_ROW int64 words per sample (include_ext/gsa_components.h).  Slots as
+# The summary row of ``despeckle(..., return_stats=True)``: COMP_ROW int64 words per sample (include/gsa_components.h).  Slots as
 # pair_stats: slot k < 8 is mask value k, slot 8 every value >= 8.
 COMP_SLOTS = 9
 COMP_NCOMP = 0              # + s: number of components whose value falls in slot s
@@ -34,7 +34,7 @@ FILL_NEIGHBOUR = -1
 CONNECTIVITIES = (4, 8)
 MAX_AREA = 2 ** 31 - 1
 
-# include_ops/gsa_boundary.h
+# include/gsa_boundary.h
 BOUNDARY_FAR = 32767        # dist2 of a pixel with no other value within the radius
 BOUNDARY_MAX_RADIUS = 32
 
@@ -42,6 +42,16 @@ BOUNDARY_MAX_RADIUS = 32
 def _check(t, what):
     if not is_device_tensor(t, torch.uint8, dims=(2, 3)):
         raise ValueError("%s must be a contiguous uint8 CUDA tensor (H, W) or (n, H, W)" % what)
+
+
+def _other_tensor(out, what, dtype, mask):
+    """``out`` checked as the result ``what`` of ``mask``'s shape: contiguous, of ``dtype``, on the same device, not overlapping it."""
+    if not is_device_tensor(out, dtype, shape=mask.shape, device=mask.device):
+        raise ValueError("%s must be a contiguous %s tensor %s on %s" % (what, str(dtype).replace("torch.", ""), tuple(mask.shape), mask.device))
+    a, b, size, other = mask.data_ptr(), out.data_ptr(), mask.numel(), out.numel() * out.element_size()
+    if out is mask or (size and a < b + other and b < a + size):
+        raise ValueError("%s must not be, or overlap, the input mask" % what)
+    return out
 
 
 def morph_mask(mask, out=None):
@@ -54,18 +64,9 @@ def morph_mask(mask, out=None):
     n = mask.shape[0] if mask.dim() == 3 else 1
     if not 1 <= H <= MAX_EXTENT or not 1 <= W <= MAX_EXTENT:
         raise ValueError("morph_mask takes masks whose sides are 1..%d px, got %dx%d" % (MAX_EXTENT, H, W))
-    dev = mask.device
-    if out is not None:
-        _check(out, "out")
-        if tuple(out.shape) != tuple(mask.shape) or out.device != dev:
-            raise ValueError("out must be a contiguous uint8 tensor %s on %s" % (tuple(mask.shape), dev))
-        a, b, size = mask.data_ptr(), out.data_ptr(), mask.numel()
-        if out is mask or (size and a < b + size and b < a + size):
-            raise ValueError("out must not be, or overlap, the input mask")
-    if out is None:
-        out = torch.empty_like(mask)
+    out = torch.empty_like(mask) if out is None else _other_tensor(out, "out", torch.uint8, mask)
     if n:
-        launch("gsa_mask_morph", dev, n, H, W, mask.data_ptr(), out.data_ptr())
+        launch("gsa_mask_morph", mask.device, n, H, W, mask.data_ptr(), out.data_ptr())
     return out
 
 
@@ -119,7 +120,7 @@ def components(mask, connectivity=8):
     pixel the smallest raster index ``y * W + x`` of its connected component (its first pixel) and the component's pixel count.  A
     component is a maximal set of pixels of equal raw value joined by horizontal and vertical steps (``connectivity=4``) or by
     diagonal ones as well (8, cv2's default and ours); every value forms components, 0 included; every image of a batch is a plane
-    of its own (the rule of include_ext/gsa_components.h).  Enqueued on the current stream of ``mask``'s device; the input is not
+    of its own (the rule of include/gsa_components.h).  Enqueued on the current stream of ``mask``'s device; the input is not
     written.  ValueError on anything else; no CPU fallback."""
     n, H, W = _plane_shape(mask, "components")
     connectivity = check_connectivity(connectivity)
@@ -145,20 +146,14 @@ def despeckle(mask, min_area, connectivity=8, fill="neighbour", out=None, return
     input is not written.  ValueError on anything else; no CPU fallback."""
     n, H, W = _plane_shape(mask, "despeckle")
     min_area, connectivity, fill = check_min_area(min_area), check_connectivity(connectivity), check_fill(fill)
-    dev = mask.device
     if out is not None:
-        _check(out, "out")
-        if tuple(out.shape) != tuple(mask.shape) or out.device != dev:
-            raise ValueError("out must be a contiguous uint8 tensor %s on %s" % (tuple(mask.shape), dev))
-        a, b, size = mask.data_ptr(), out.data_ptr(), mask.numel()
-        if out is mask or (size and a < b + size and b < a + size):
-            raise ValueError("out must not be, or overlap, the input mask")
+        _other_tensor(out, "out", torch.uint8, mask)
     labels, areas = _scratch_pair(scratch, mask)
     if out is None:
         out = torch.empty_like(mask)
-    rows = torch.empty((n, COMP_ROW), dtype=torch.int64, device=dev) if return_stats else None
+    rows = torch.empty((n, COMP_ROW), dtype=torch.int64, device=mask.device) if return_stats else None
     if n:
-        launch("gsa_mask_components", dev, n, H, W, connectivity, min_area, fill, mask.data_ptr(), labels.data_ptr(), areas.data_ptr(),
+        launch("gsa_mask_components", mask.device, n, H, W, connectivity, min_area, fill, mask.data_ptr(), labels.data_ptr(), areas.data_ptr(),
                out.data_ptr(), rows.data_ptr() if return_stats else None)
     if return_stats:
         return out, (rows[0] if mask.dim() == 2 else rows)
@@ -187,21 +182,11 @@ def _radius(v, what):
     return r
 
 
-def _other_tensor(out, what, dtype, mask):
-    """``out`` checked as the result ``what`` of ``mask``'s shape: contiguous, of ``dtype``, on the same device, not overlapping it."""
-    if not is_device_tensor(out, dtype, shape=mask.shape, device=mask.device):
-        raise ValueError("%s must be a contiguous %s tensor %s on %s" % (what, str(dtype).replace("torch.", ""), tuple(mask.shape), mask.device))
-    a, b, size, other = mask.data_ptr(), out.data_ptr(), mask.numel(), out.numel() * out.element_size()
-    if out is mask or (size and a < b + other and b < a + size):
-        raise ValueError("%s must not be, or overlap, the input mask" % what)
-    return out
-
-
 def boundary_distance(mask, max_radius=BOUNDARY_MAX_RADIUS, out=None):
     """mask (H, W) or (n, H, W) contiguous uint8 CUDA tensor -> an int16 tensor of the same shape (new, or ``out``): every pixel's
     squared Euclidean distance to the nearest pixel of its plane with another raw value where that is at most ``max_radius``^2
     (``max_radius`` 1..32), and ``BOUNDARY_FAR`` (32767) elsewhere.  The outside of the image is not another value: an image edge
-    makes no boundary, and a constant plane is FAR everywhere (the rule of include_ops/gsa_boundary.h).  What boundary-weighted
+    makes no boundary, and a constant plane is FAR everywhere (the rule of include/gsa_boundary.h).  What boundary-weighted
     losses, one-sided bands and trimaps are built from.  Enqueued on the current stream of ``mask``'s device; the input is not
     written.  ValueError on anything else; no CPU fallback."""
     n, H, W = _plane_shape(mask, "boundary_distance")

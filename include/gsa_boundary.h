@@ -4,9 +4,6 @@
  * of an ignore label around every class boundary.  The reference has no kernel for it; its dataset readers
  * map a stored 255 to -1, as VOC's void border asks, and that is the value the band is meant to write.
  *
- * (This header lives in include_ops/: the sets of headers under include/ and include_ext/ are pinned by the ABI tests.  The set
- * under include_ops/ is checked against the keys of _lib.OPS_SIGNATURES, so the next header goes here too.)
- *
  * The rule (canonical, all integers).  Input: mask (n, H, W) u8; every image is a plane of its own.  R = radius, 1..32.
  *
  *   D(p)     = min over pixels q of the SAME plane with mask[q] != mask[p] (raw u8 values) of (qy-py)^2 + (qx-px)^2;

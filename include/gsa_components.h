@@ -4,8 +4,6 @@
  * section 17).  The reference has no counterpart: its utils.morph_mask (include/gsa_mask.h) removes what fits inside a 5x5 window
  * and nothing larger.
  *
- * (This header lives in include_ext/, beside include/: the set of headers under include/ is pinned by the ABI tests.)
- *
  * The rule (canonical, all integers).  Input: mask (n, H, W) u8; every image is a plane of its own.
  *
  *   connectivity  4 or 8.  Two pixels are neighbours if they differ by one step horizontally or vertically; with 8 a diagonal step

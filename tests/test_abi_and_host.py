@@ -23,13 +23,14 @@ def hip_library():
 
 
 HEADERS = ("gsa.h", "gsa_train.h", "gsa_jpeg.h", "gsa_jpeg_roundtrip.h", "gsa_png.h", "gsa_augment.h", "gsa_mask.h",
-           "gsa_photometric.h", "gsa_stats.h")
+           "gsa_photometric.h", "gsa_stats.h", "gsa_components.h", "gsa_boundary.h")
 
 
 @pytest.mark.parametrize("header", HEADERS)
 def test_header_exports_and_table_agree(hip_library, header):
     """include/<header> <-> the library's exports <-> the header's group of _lib.SIGNATURES: the same names, every one exported, and
-    bound with a result and arguments of the declared kinds, position by position (tests/common.py names the kinds)."""
+    bound with a result and arguments of the declared kinds, position by position (tests/common.py names the kinds); the cached
+    ``load_library()`` resolves every one too."""
     declared = header_declarations(header)[1]
     assert set(declared) == set(_lib.SIGNATURES[header])
     lib, api = ctypes.CDLL(hip_library), _lib.Api(hip_library, "gsa_")
@@ -37,17 +38,31 @@ def test_header_exports_and_table_agree(hip_library, header):
         assert hasattr(lib, name), "%s declared in %s but not exported" % (name, header)
         fn = api.fn(name)
         assert (ctypes_kind(fn.restype), [ctypes_kind(t) for t in fn.argtypes]) == kinds, name
+        assert _lib.load_library().fn(name) is not None
 
 
 def test_header_symbols_are_exported(hip_library):
-    """The table knows every header under include/ and every function of all of them once; what include/gsa.h declares is an
-    attribute of the Api without its prefix."""
+    """The table knows every header under include/ and every function of all of them once; include/ is the only header directory;
+    what include/gsa.h declares is an attribute of the Api without its prefix."""
     assert sorted(os.listdir(os.path.join(ROOT, "include"))) == sorted(HEADERS) == sorted(_lib.SIGNATURES)
-    assert sum(len(header_declarations(h)[1]) for h in HEADERS) == len({n for g in _lib.SIGNATURES.values() for n in g}) == 55
+    assert [d for d in os.listdir(ROOT) if d.startswith("include") and os.path.isdir(os.path.join(ROOT, d))] == ["include"]
+    assert sum(len(header_declarations(h)[1]) for h in HEADERS) == len({n for g in _lib.SIGNATURES.values() for n in g}) == 57
     api = _lib.Api(hip_library, "gsa_")
     for name in header_declarations("gsa.h")[1]:
         assert getattr(api, name[len("gsa_"):]) is api.fn(name)
     assert b"gfx950" in api.version()
+
+
+def test_makefile_unit_list_is_the_source_files():
+    """csrc/Makefile builds every library from its one UNITS line: the stems there are the .hip and .cpp files of csrc/, each once.
+    A unit left out would otherwise show as an unresolved symbol only when the library is loaded."""
+    csrc = os.path.join(ROOT, "gan-segmentation_amd", "csrc")
+    with open(os.path.join(csrc, "Makefile")) as f:
+        lines = re.findall(r"^UNITS\s*=\s*(.*)$", f.read(), flags=re.M)
+    assert len(lines) == 1 and not lines[0].endswith("\\")
+    units = lines[0].split()
+    sources = [os.path.splitext(fn) for fn in os.listdir(csrc)]
+    assert sorted(units) == sorted(stem for stem, ext in sources if ext in (".hip", ".cpp")) and len(units) == len(set(units))
 
 
 def test_training_header_symbols_are_exported():

@@ -1,21 +1,17 @@
-"""The mask boundary distance and the ignore band without a GPU (include_ops/gsa_boundary.h; mask_ops.boundary_distance / ignore_band;
+"""The mask boundary distance and the ignore band without a GPU (include/gsa_boundary.h; mask_ops.boundary_distance / ignore_band;
 ImageGenerator(mask_ignore_band=...); the MASK_IGNORE_BAND and MASK_IGNORE_LABEL keys).
 
 ``rule_boundary(m, R)`` is the canonical rule in its separable form, in numpy: the vertical distance h to the nearest other value of
 the column, then the minimum over |dx| <= R of dx^2 + (other value ? 0 : h^2).  ``rule_band(m, R, label)`` is the band.  The rule is
 PINNED here, with zero differences allowed, against a brute-force search of the (2R+1)^2 window and, where scipy imports, against
 ``scipy.ndimage.distance_transform_edt`` taken per value, squared and rounded.  The GPU tests (tests/test_gpu_boundary.py) hold the
-kernel to this rule over every pixel.  Also here: hand cases, the table of include_ops/ against the headers' text and the library's
-exports, the entry's argument checks, and the validation of the keywords and the keys."""
-import os
-
+kernel to this rule over every pixel.  Also here: hand cases, the header's one entry and its macros, the entry's argument
+checks, and the validation of the keywords and the keys."""
 import numpy as np
 import pytest
 
-from tests.test_downscale_host import _config
+from tests.test_downscale_host import _ModelLoaded, _config, no_models  # noqa: F401  (no_models is a fixture)
 from tests.test_mask_morph_host import _blur
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FAR = 32767
 MAX_RADIUS = 32
@@ -241,25 +237,12 @@ def test_every_image_of_a_batch_is_a_plane_of_its_own():
 
 
 # -- the C ABI -----------------------------------------------------------------------------------------------------------------
-def test_ops_table_matches_the_headers(hip_library):
-    """The directory listing against the table's keys (no literal list: the next header needs no fourth directory); every header's
-    declarations against its group and the library's exports, kind by kind; the macros against the Python constants."""
-    import ctypes
-    from gan_segmentation_amd import _lib, mask_ops
-    from tests.common import ctypes_kind, header_declarations
-    assert sorted(os.listdir(os.path.join(ROOT, "include_ops"))) == sorted(_lib.OPS_SIGNATURES)
-    assert "gsa_boundary.h" in _lib.OPS_SIGNATURES
-    lib = ctypes.CDLL(hip_library)
-    others = {n for table in (_lib.SIGNATURES, _lib.EXT_SIGNATURES) for g in table.values() for n in g}
-    for header, table in _lib.OPS_SIGNATURES.items():
-        text, declared = header_declarations("../include_ops/" + header)
-        assert set(declared) == set(table) and table, header
-        for name, (res, args) in table.items():
-            assert hasattr(lib, name), "%s is not exported" % name
-            assert (ctypes_kind(res), [ctypes_kind(a) for a in args]) == declared[name], name
-            assert name not in others, "%s is bound twice" % name
-            assert _lib.load_library().fn(name) is not None
-    text, declared = header_declarations("../include_ops/gsa_boundary.h")
+def test_boundary_header_symbols_and_macros():
+    """include/gsa_boundary.h declares the one entry (tests/test_abi_and_host.py checks its export and its ctypes row), and its
+    macros are the Python constants."""
+    from gan_segmentation_amd import mask_ops
+    from tests.common import header_declarations
+    text, declared = header_declarations("gsa_boundary.h")
     assert set(declared) == {"gsa_mask_boundary"}
     for macro, value in (("FAR", mask_ops.BOUNDARY_FAR), ("MAX_RADIUS", mask_ops.BOUNDARY_MAX_RADIUS)):
         assert "#define GSA_BOUNDARY_%s %d " % (macro, value) in text.replace("\n", " \n"), macro
@@ -333,20 +316,6 @@ def test_keywords_accept_and_default_to_off():
         p = inspect.signature(fn).parameters
         assert (p["mask_ignore_band"].default, p["mask_ignore_label"].default) == (0, 255)
         assert list(p)[-2:] == ["mask_ignore_band", "mask_ignore_label"], "the new parameters go last"
-
-
-class _ModelLoaded(Exception):
-    pass
-
-
-@pytest.fixture
-def no_models(monkeypatch):
-    """`main.py generate` stops where it would load the first model."""
-    from gan_segmentation_amd import seg_solver
-
-    def refuse(*args, **kwargs):
-        raise _ModelLoaded()
-    monkeypatch.setattr(seg_solver, "SegSolver", refuse)
 
 
 @pytest.mark.parametrize("key,value,name", [("MASK_IGNORE_BAND", -2, "mask_ignore_band"), ("MASK_IGNORE_BAND", 33, "mask_ignore_band"),

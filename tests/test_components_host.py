@@ -1,4 +1,4 @@
-"""The mask components without a GPU (include_ext/gsa_components.h; mask_ops.components / despeckle; ImageGenerator(mask_min_area=...);
+"""The mask components without a GPU (include/gsa_components.h; mask_ops.components / despeckle; ImageGenerator(mask_min_area=...);
 the MASK_MIN_AREA, MASK_CONNECTIVITY and MASK_FILL keys).
 
 ``rule_components(m, connectivity)`` is the canonical rule: a plain raster union-find over pixels of equal raw value.  It is the
@@ -7,7 +7,7 @@ allowed, against
 * a scipy.ndimage.label form (per value; ndimage.minimum of the raster index per label; bincount areas),
 * a committed fixture (tests/golden/mask_components.npz), which holds without scipy.
 The GPU tests (tests/test_gpu_components.py) hold the kernels to this rule over every pixel and every row word.  Also here: hand
-cases, the extension table against the header's text, the library's export and the validation of the keywords and the keys."""
+cases, the header's one entry and its macros, the entry's argument checks and the validation of the keywords and the keys."""
 import os
 
 import numpy as np
@@ -378,20 +378,13 @@ def test_every_image_of_a_batch_is_a_plane_of_its_own():
 
 
 # -- the C ABI -----------------------------------------------------------------------------------------------------------------
-def test_extension_table_matches_the_header(hip_library):
-    import ctypes
-    from gan_segmentation_amd import _lib, mask_ops
-    from tests.common import ctypes_kind, header_declarations
-    text, declared = header_declarations("../include_ext/gsa_components.h")
-    assert sorted(os.listdir(os.path.join(ROOT, "include_ext"))) == sorted(_lib.EXT_SIGNATURES) == ["gsa_components.h"]
-    table = _lib.EXT_SIGNATURES["gsa_components.h"]
-    assert set(declared) == set(table) == {"gsa_mask_components"}
-    lib = ctypes.CDLL(hip_library)
-    for name, (res, args) in table.items():
-        assert hasattr(lib, name), "%s is not exported" % name
-        assert (ctypes_kind(res), [ctypes_kind(a) for a in args]) == declared[name], name
-    assert not set(table) & {n for g in _lib.SIGNATURES.values() for n in g}
-    assert _lib.load_library().fn("gsa_mask_components") is not None
+def test_components_header_symbols_and_macros():
+    """include/gsa_components.h declares the one entry (tests/test_abi_and_host.py checks its export and its ctypes row), and its
+    macros are the Python constants."""
+    from gan_segmentation_amd import mask_ops
+    from tests.common import header_declarations
+    text, declared = header_declarations("gsa_components.h")
+    assert set(declared) == {"gsa_mask_components"}
     for macro, value in (("SLOTS", mask_ops.COMP_SLOTS), ("NCOMP", mask_ops.COMP_NCOMP), ("LARGEST", mask_ops.COMP_LARGEST),
                          ("SMALL", mask_ops.COMP_SMALL), ("SMALL_PIXELS", mask_ops.COMP_SMALL_PIXELS), ("ROW", mask_ops.COMP_ROW)):
         assert "#define GSA_COMP_%s %d " % (macro, value) in text.replace("\n", " \n"), macro

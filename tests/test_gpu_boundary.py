@@ -1,4 +1,4 @@
-"""The mask boundary distance and the ignore band on the GPU (include_ops/gsa_boundary.h gsa_mask_boundary; mask_ops.boundary_distance /
+"""The mask boundary distance and the ignore band on the GPU (include/gsa_boundary.h gsa_mask_boundary; mask_ops.boundary_distance /
 ignore_band; ImageGenerator(mask_ignore_band=...); the MASK_IGNORE_BAND key): every pixel of dist2 AND of out against the rule of
 tests/test_boundary_host.py -- nothing is excluded.  Except on the constant and checkerboard planes every case asserts that its
 expected result holds both FAR and non-FAR pixels."""

@@ -1,4 +1,4 @@
-"""The mask components on the GPU (include_ext/gsa_components.h gsa_mask_components; mask_ops.components / despeckle;
+"""The mask components on the GPU (include/gsa_components.h gsa_mask_components; mask_ops.components / despeckle;
 ImageGenerator(mask_min_area=...); the MASK_MIN_AREA key): every pixel of labels, areas and out and every word of the rows against
 the rule of tests/test_components_host.py -- nothing is excluded.  The oracle is the scipy form where scipy is importable and the
 raster union-find otherwise; the host tests pin the two equal."""

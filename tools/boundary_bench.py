@@ -1,4 +1,4 @@
-"""Cost of the mask boundary distance and the ignore band (csrc/gsa_boundary.hip, include_ops/gsa_boundary.h) on generated masks,
+"""Cost of the mask boundary distance and the ignore band (csrc/gsa_boundary.hip, include/gsa_boundary.h) on generated masks,
 bench.py's synthetic weights.
 
 Kernel mode (default): one mask batch from the decoder, then for every radius of --radii ROUNDS blocks of ITERS calls of

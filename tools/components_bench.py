@@ -1,4 +1,4 @@
-"""Cost of the mask components (csrc/gsa_components.hip, include_ext/gsa_components.h) on generated masks, bench.py's synthetic weights.
+"""Cost of the mask components (csrc/gsa_components.hip, include/gsa_components.h) on generated masks, bench.py's synthetic weights.
 
 Kernel mode (default): one mask batch -- the decoder's (--input decoder) or the serpentine, the union-find's worst case (--input
 serpentine) -- then ROUNDS blocks of ITERS calls of mask_ops.despeckle with rows, each block timed with device events; prints the

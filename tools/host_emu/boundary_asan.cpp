@@ -8,7 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "../../include_ops/gsa_boundary.h"
+#include "../../include/gsa_boundary.h"
 
 static int brute(const uint8_t* m, int H, int W, int y, int x, int R) {
     int best = GSA_BOUNDARY_FAR;
