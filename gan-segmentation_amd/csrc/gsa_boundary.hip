@@ -29,23 +29,22 @@
 
 #include "../../include/gsa.h"
 #include "../../include/gsa_boundary.h"
+#include "gsa_plane.h"
 
 namespace {
+
+using namespace gsa::plane;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 64;                       // output pixels of a workgroup: 64 x 64
 constexpr int kTileD = kTile / 4;               // 16 dwords of a tile row
 constexpr int kSegment = 16;                    // tile rows of a column-pass work item
 constexpr unsigned kOutside = 0x80u;            // h of a column outside the image; its square exceeds every R*R
-constexpr int kMaxExtent = 65535;
-constexpr long long kMaxTiles = 1ll << 24;      // HIP takes fewer than 2^32 threads per launch
 
 static_assert(kOutside * kOutside > GSA_BOUNDARY_MAX_RADIUS * GSA_BOUNDARY_MAX_RADIUS && GSA_BOUNDARY_MAX_RADIUS + 1 < (int)kOutside,
               "a position outside the image never comes into the band, and the cap R + 1 never looks like it");
 static_assert(GSA_BOUNDARY_MAX_RADIUS * GSA_BOUNDARY_MAX_RADIUS < GSA_BOUNDARY_FAR, "every distance in a band fits below FAR");
 static_assert(kTile % kSegment == 0 && kTile % 4 == 0, "whole segments, dword columns");
-
-__device__ __forceinline__ unsigned byte_of(unsigned w, int b) { return (w >> (8 * b)) & 255u; }
 
 // K: dwords of apron on each side (apron A = 4K pixels >= R).  LDS: (64 + 8K) x (64 + 8K) bytes of mask and 64 x (64 + 8K) bytes
 // of h -- 9.8 KB at K = 1, 24 KB at K = 8.
@@ -59,11 +58,9 @@ __global__ __launch_bounds__(kThreads) void mask_boundary_kernel(const uint8_t* 
     constexpr int kCols = 4 * kColsD;           // staged byte columns
     __shared__ unsigned lds_m[kRows * kColsD];
     __shared__ unsigned lds_h[kTile * kColsD];
-    const int plane = blockIdx.x / tiles_per_plane;                     // uniform over the workgroup
-    const int tile = blockIdx.x - plane * tiles_per_plane;
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-    const int y0 = tile_y * kTile, x0 = tile_x * kTile;
-    const size_t plane_at = (size_t)plane * H * W;
+    const Tile tl = tile_of(tiles_x, tiles_per_plane);                  // uniform over the workgroup
+    const int y0 = tl.tile_y * kTile, x0 = tl.tile_x * kTile;
+    const size_t plane_at = (size_t)tl.plane * H * W;
     const uint8_t* __restrict__ plane_in = mask + plane_at;             // every image is a plane of its own: no tap leaves it
 
     // stage the tile and its apron; what lies outside the image is never read as a value (0 keeps the LDS defined)
@@ -180,50 +177,31 @@ __global__ __launch_bounds__(kThreads) void mask_boundary_kernel(const uint8_t* 
     }
 }
 
-template <int K>
-void launch(bool aligned, dim3 grid, hipStream_t s, const uint8_t* mask, int16_t* dist2, uint8_t* out, int H, int W, int R, unsigned label,
-            int tiles_x, int tiles_per_plane) {
-    if (aligned)
-        hipLaunchKernelGGL((mask_boundary_kernel<K, true>), grid, dim3(kThreads), 0, s, mask, dist2, out, H, W, R, label, tiles_x,
-                           tiles_per_plane);
-    else
-        hipLaunchKernelGGL((mask_boundary_kernel<K, false>), grid, dim3(kThreads), 0, s, mask, dist2, out, H, W, R, label, tiles_x,
-                           tiles_per_plane);
-}
-
-bool overlap(uintptr_t a, uint64_t a_bytes, uintptr_t b, uint64_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; }
-
 }  // namespace
 
 extern "C" {
 
 int gsa_mask_boundary(void* stream, int32_t n, int32_t H, int32_t W, int32_t radius, int32_t label, const uint8_t* mask, int16_t* dist2,
                       uint8_t* out) {
-    if (n < 0 || H < 1 || W < 1 || H > kMaxExtent || W > kMaxExtent || (long long)H * W >= (1ll << 31)) return GSA_ERR_INVALID;
+    if (n < 0 || !extent_ok_31(H, W)) return GSA_ERR_INVALID;
     if (radius < 1 || radius > GSA_BOUNDARY_MAX_RADIUS || label < 0 || label > 255) return GSA_ERR_INVALID;
     if (n == 0) return GSA_OK;
     if (!mask || (!dist2 && !out)) return GSA_ERR_INVALID;
     const uint64_t pixels = (uint64_t)n * (uint64_t)H * (uint64_t)W;
     const uintptr_t a = reinterpret_cast<uintptr_t>(mask), b = reinterpret_cast<uintptr_t>(out), c = reinterpret_cast<uintptr_t>(dist2);
     if (c & 1) return GSA_ERR_INVALID;
-    if (out && overlap(a, pixels, b, pixels)) return GSA_ERR_INVALID;
-    if (dist2 && overlap(a, pixels, c, 2 * pixels)) return GSA_ERR_INVALID;
-    if (out && dist2 && overlap(b, pixels, c, 2 * pixels)) return GSA_ERR_INVALID;
-    const long long tiles_x = (W + kTile - 1) / kTile;
-    const long long tiles_per_plane = tiles_x * ((H + kTile - 1) / kTile);
-    if (tiles_per_plane * n >= kMaxTiles) return GSA_ERR_INVALID;
+    if (out && ranges_overlap(mask, pixels, out, pixels)) return GSA_ERR_INVALID;
+    if (dist2 && ranges_overlap(mask, pixels, dist2, 2 * pixels)) return GSA_ERR_INVALID;
+    if (out && dist2 && ranges_overlap(out, pixels, dist2, 2 * pixels)) return GSA_ERR_INVALID;
+    const TileGrid g = tile_grid(H, W, kTile, kTile);
+    if (g.per_plane * n >= kMaxWorkgroups) return GSA_ERR_INVALID;     // refused, not split
     const bool aligned = W % 4 == 0 && ((a | b) & 3) == 0 && (c & 7) == 0;     // a null pointer is aligned
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(tiles_per_plane * n));
-    const unsigned lab = (unsigned)label;
-    if (radius <= 4)
-        launch<1>(aligned, grid, s, mask, dist2, out, H, W, radius, lab, (int)tiles_x, (int)tiles_per_plane);
-    else if (radius <= 8)
-        launch<2>(aligned, grid, s, mask, dist2, out, H, W, radius, lab, (int)tiles_x, (int)tiles_per_plane);
-    else if (radius <= 16)
-        launch<4>(aligned, grid, s, mask, dist2, out, H, W, radius, lab, (int)tiles_x, (int)tiles_per_plane);
-    else
-        launch<8>(aligned, grid, s, mask, dist2, out, H, W, radius, lab, (int)tiles_x, (int)tiles_per_plane);
+    const auto kernel = radius <= 4    ? (aligned ? mask_boundary_kernel<1, true> : mask_boundary_kernel<1, false>)
+                        : radius <= 8  ? (aligned ? mask_boundary_kernel<2, true> : mask_boundary_kernel<2, false>)
+                        : radius <= 16 ? (aligned ? mask_boundary_kernel<4, true> : mask_boundary_kernel<4, false>)
+                                       : (aligned ? mask_boundary_kernel<8, true> : mask_boundary_kernel<8, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(g.per_plane * n)), dim3(kThreads), 0, (hipStream_t)stream, mask, dist2, out, H, W, (int)radius,
+                       (unsigned)label, (int)g.tiles_x, (int)g.per_plane);
     return hipGetLastError() == hipSuccess ? GSA_OK : GSA_ERR_HIP;
 }
 

@@ -35,8 +35,11 @@
 
 #include "../../include/gsa.h"
 #include "../../include/gsa_components.h"
+#include "gsa_plane.h"
 
 namespace {
+
+using namespace gsa::plane;
 
 constexpr int kThreads = 256;
 constexpr int kTileW = 64;                      // a tile row is one wave's worth of labels: 256 contiguous bytes
@@ -48,8 +51,6 @@ constexpr int kSameRootRounds = 4;              // phase 1: shared roots a wave 
 constexpr int kBlockPix = 16 * kThreads;        // phases 3 and 4: consecutive pixels of a workgroup, 16 per thread.  A workgroup sends its
                                                 // partial row words on with a few atomics, and atomics on one row's cache line run one
                                                 // after the other chip-wide (measured: DESIGN.md section 17) -- few, fat workgroups
-constexpr int kMaxExtent = 65535;
-constexpr long long kMaxBlocks = (1ll << 24) - 1;      // HIP takes fewer than 2^32 threads per launch
 
 static_assert(kPerThread == kSeg && kTileW % kSeg == 0 && kThreads == kTileH * (kTileW / kSeg), "a thread per 16-px row segment");
 static_assert(kTileW % 4 == 0, "dword loads of a segment");
@@ -108,16 +109,14 @@ __global__ __launch_bounds__(kThreads) void label_tiles_kernel(const uint8_t* __
     __shared__ int cnt[kTilePix];               // pixels of the tile component whose local root is the index; 0 elsewhere
     __shared__ unsigned val4[kTilePix / 4];     // the tile's values, one byte per pixel; 0 outside the image (never compared)
     const uint8_t* val = reinterpret_cast<const uint8_t*>(val4);
-    const int plane = blockIdx.x / tiles_per_plane;                     // uniform over the workgroup
-    const int tile = blockIdx.x - plane * tiles_per_plane;
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-    const int y0 = tile_y * kTileH, x0 = tile_x * kTileW;
-    const size_t base = (size_t)plane * H * W;                          // every image is a plane of its own
+    const Tile t = tile_of(tiles_x, tiles_per_plane);                   // uniform over the workgroup
+    const int y0 = t.tile_y * kTileH, x0 = t.tile_x * kTileW;
+    const size_t base = (size_t)t.plane * H * W;                        // every image is a plane of its own
     const uint8_t* __restrict__ pm = mask + base;
     int* __restrict__ pl = labels + base;
     int* __restrict__ pa = areas + base;
 
-    if (rows && tile == 0 && threadIdx.x < GSA_COMP_ROW) rows[(size_t)plane * GSA_COMP_ROW + threadIdx.x] = 0;
+    if (rows && t.tile == 0 && threadIdx.x < GSA_COMP_ROW) rows[(size_t)t.plane * GSA_COMP_ROW + threadIdx.x] = 0;
 
     // pass 1: a thread loads its 16-px row segment and labels every pixel with the start of its horizontal run inside the segment
     {
@@ -143,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void label_tiles_kernel(const uint8_t* __
         unsigned prev = 0;
 #pragma unroll
         for (int k = 0; k < kSeg; ++k) {
-            const unsigned v = (w[k >> 2] >> (8 * (k & 3))) & 255u;
+            const unsigned v = byte_of(w[k >> 2], k & 3);
             if (k == 0 || v != prev) run = i0 + k;
             lab[i0 + k] = run;
             cnt[i0 + k] = 0;
@@ -351,41 +350,33 @@ extern "C" {
 
 int gsa_mask_components(void* stream, int32_t n, int32_t H, int32_t W, int32_t connectivity, int32_t min_area, int32_t fill,
                         const uint8_t* mask, int32_t* labels, int32_t* areas, uint8_t* out, int64_t* rows) {
-    if (n < 0 || H < 1 || W < 1 || H > kMaxExtent || W > kMaxExtent || (long long)H * W >= (1ll << 31)) return GSA_ERR_INVALID;
+    if (n < 0 || !extent_ok_31(H, W)) return GSA_ERR_INVALID;
     if ((connectivity != 4 && connectivity != 8) || min_area < 0 || fill < GSA_COMP_FILL_NEIGHBOUR || fill > 255) return GSA_ERR_INVALID;
     if (n == 0) return GSA_OK;
     if (!mask || !labels || !areas) return GSA_ERR_INVALID;
     const uint64_t plane_px = (uint64_t)H * (uint64_t)W, bytes = (uint64_t)n * plane_px;        // n * H * W in 64 bits
-    if (out) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(mask), b = reinterpret_cast<uintptr_t>(out);
-        if (a < b + bytes && b < a + bytes) return GSA_ERR_INVALID;    // the ranges overlap
-    }
+    if (out && ranges_overlap(mask, bytes, out, bytes)) return GSA_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     const int HW = (int)plane_px, conn8 = connectivity == 8;
-    const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
-    const long long tiles = (long long)tiles_x * tiles_y;                               // workgroups of phase 1, per plane
+    const TileGrid g = tile_grid(H, W, kTileW, kTileH);
+    const int tiles_x = (int)g.tiles_x, tiles_y = (int)g.tiles_y;
+    const long long tiles = g.per_plane;                                                // workgroups of phase 1, per plane
     const long long seam_px = (long long)(tiles_y - 1) * W + (long long)(tiles_x - 1) * H;
     const long long seam_blocks = (seam_px + kThreads - 1) / kThreads;                   // phase 2; 0: one tile, nothing to merge
     const long long px_blocks = ((long long)HW + kBlockPix - 1) / kBlockPix;             // phases 3 and 4; at most 2^19
     long long most = tiles > px_blocks ? tiles : px_blocks;                             // tiles <= 2^10 * 2^10 + ... : far below 2^24
     if (seam_blocks > most) most = seam_blocks;
-    if (most > kMaxBlocks) return GSA_ERR_INVALID;
-    const long long planes_per_launch = kMaxBlocks / most;
-    const bool aligned = W % 4 == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+    if (most >= kMaxWorkgroups) return GSA_ERR_INVALID;
+    const auto label_tiles = W % 4 == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0 ? label_tiles_kernel<true> : label_tiles_kernel<false>;
     const dim3 block(kThreads);
-    for (long long first = 0; first < n; first += planes_per_launch) {
-        const long long planes = n - first < planes_per_launch ? n - first : planes_per_launch;
+    for_each_launch(n, most, [&](long long first, long long planes) {      // split, not refused
         const size_t off = (size_t)first * plane_px;
         const uint8_t* mk = mask + off;
         int* lb = labels + off;
         int* ar = areas + off;
         uint8_t* ot = out ? out + off : nullptr;
         long long* rw = rows ? reinterpret_cast<long long*>(rows) + first * GSA_COMP_ROW : nullptr;
-        const dim3 grid1((unsigned)(planes * tiles));
-        if (aligned)
-            hipLaunchKernelGGL(label_tiles_kernel<true>, grid1, block, 0, s, mk, lb, ar, rw, H, W, tiles_x, (int)tiles, conn8);
-        else
-            hipLaunchKernelGGL(label_tiles_kernel<false>, grid1, block, 0, s, mk, lb, ar, rw, H, W, tiles_x, (int)tiles, conn8);
+        hipLaunchKernelGGL(label_tiles, dim3((unsigned)(planes * tiles)), block, 0, s, mk, lb, ar, rw, H, W, tiles_x, (int)tiles, conn8);
         if (seam_blocks > 0)
             hipLaunchKernelGGL(merge_seams_kernel, dim3((unsigned)(planes * seam_blocks)), block, 0, s, mk, lb, H, W, tiles_y,
                                (int)seam_blocks, conn8);
@@ -393,7 +384,7 @@ int gsa_mask_components(void* stream, int32_t n, int32_t H, int32_t W, int32_t c
         hipLaunchKernelGGL(flatten_count_kernel, grid_px, block, 0, s, mk, lb, ar, rw, HW, (int)px_blocks);
         hipLaunchKernelGGL(spread_filter_kernel, grid_px, block, 0, s, mk, lb, ar, ot, rw, W, HW, (int)px_blocks,
                            (int)min_area, (int)fill);
-    }
+    });
     return hipGetLastError() == hipSuccess ? GSA_OK : GSA_ERR_HIP;
 }
 

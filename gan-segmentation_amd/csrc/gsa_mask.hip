@@ -24,8 +24,11 @@
 
 #include "../../include/gsa.h"
 #include "../../include/gsa_mask.h"
+#include "gsa_plane.h"
 
 namespace {
+
+using namespace gsa::plane;
 
 constexpr int kThreads = 256;
 constexpr int kTileW = 64;                      // output pixels of a workgroup: 64 x 64.  With the 8-px apron it stages 80 x 80 (1.56 x
@@ -35,8 +38,6 @@ constexpr int kRows = kTileH + 2 * kApron;      // 80 staged rows
 constexpr int kTileD = kTileW / 4;              // 16 dwords of a tile row
 constexpr int kFirstD = 1 + kApron / 4;         // 3: dword column of the tile's first pixel -- one filler column, two of apron
 constexpr int kCols = kTileD + 2 * kFirstD;     // 22 dword columns: filler, apron, tile, apron, filler
-constexpr int kMaxExtent = 65535;
-constexpr long long kMaxTiles = 1ll << 24;      // HIP takes fewer than 2^32 threads per launch
 
 static_assert(kTileW % 4 == 0 && kTileH % 4 == 0 && kApron % 4 == 0, "dword columns, 4-row blocks");
 
@@ -64,9 +65,6 @@ __device__ __forceinline__ void window4(const unsigned (&v)[4 + 2 * R], unsigned
         o[3] = op3<MX>(c, hi, v[11]);
     }
 }
-
-__device__ __forceinline__ unsigned byte_of(unsigned w, int b) { return (w >> (8 * b)) & 255u; }
-__device__ __forceinline__ unsigned pack4(const unsigned (&o)[4]) { return o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24); }
 
 // 0xff in every byte of the dword at (gy, gx .. gx+3) that lies outside the H x W image.
 __device__ __forceinline__ unsigned outside_mask(int gy, int gx, int H, int W) {
@@ -130,14 +128,7 @@ __device__ __forceinline__ void col_pass(const unsigned* __restrict__ src, unsig
                 const unsigned m = outside_mask(gy, gx, H, W);
                 dst[(j0 + r) * kCols + d] = next_identity ? (res[r] | m) : (res[r] & ~m);
             } else if (gy < H && gx < W) {      // the tile's own pixels: gy, gx >= 0
-                uint8_t* q = plane_out + (size_t)gy * W + gx;
-                if (ALIGNED) {                  // W % 4 == 0: the dword is inside as a whole
-                    *reinterpret_cast<unsigned*>(q) = res[r];
-                } else {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b)
-                        if (gx + b < W) q[b] = (uint8_t)byte_of(res[r], b);
-                }
+                store_px4<ALIGNED>(plane_out + (size_t)gy * W, gx, W, res[r]);
             }
         }
     }
@@ -147,28 +138,17 @@ template <bool ALIGNED>
 __global__ __launch_bounds__(kThreads) void mask_morph_kernel(const uint8_t* __restrict__ mask, uint8_t* __restrict__ out, int H, int W,
                                                               int tiles_x, int tiles_per_plane) {
     __shared__ unsigned lds_a[kRows * kCols], lds_b[kRows * kCols];
-    const int plane = blockIdx.x / tiles_per_plane;                     // uniform over the workgroup
-    const int tile = blockIdx.x - plane * tiles_per_plane;
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
-    const int y0 = tile_y * kTileH, x0 = tile_x * kTileW;
-    const uint8_t* __restrict__ plane_in = mask + (size_t)plane * H * W;   // every image is a plane of its own: no tap leaves it
-    uint8_t* __restrict__ plane_out = out + (size_t)plane * H * W;
+    const Tile t = tile_of(tiles_x, tiles_per_plane);                   // uniform over the workgroup
+    const int y0 = t.tile_y * kTileH, x0 = t.tile_x * kTileW;
+    const uint8_t* __restrict__ plane_in = mask + (size_t)t.plane * H * W;  // every image is a plane of its own: no tap leaves it
+    uint8_t* __restrict__ plane_out = out + (size_t)t.plane * H * W;
 
     // stage the tile and its apron; 0 (the first dilation's identity) outside the image and in the two filler columns
     for (int i = threadIdx.x; i < kRows * kCols; i += kThreads) {
         const int j = i / kCols, d = i % kCols;
         const int gy = y0 - kApron + j, gx = x0 + 4 * (d - kFirstD);
         unsigned v = 0;
-        if (d != 0 && d != kCols - 1 && (unsigned)gy < (unsigned)H) {
-            const uint8_t* p = plane_in + (size_t)gy * W;
-            if (ALIGNED) {
-                if ((unsigned)gx < (unsigned)W) v = *reinterpret_cast<const unsigned*>(p + gx);
-            } else {
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    if ((unsigned)(gx + b) < (unsigned)W) v |= (unsigned)p[gx + b] << (8 * b);
-            }
-        }
+        if (d != 0 && d != kCols - 1 && (unsigned)gy < (unsigned)H) v = load_px4<ALIGNED>(plane_in + (size_t)gy * W, gx, W);
         lds_a[i] = v;
     }
     __syncthreads();
@@ -193,22 +173,18 @@ __global__ __launch_bounds__(kThreads) void mask_morph_kernel(const uint8_t* __r
 extern "C" {
 
 int gsa_mask_morph(void* stream, int32_t n, int32_t H, int32_t W, const uint8_t* mask, uint8_t* out) {
-    if (n < 0 || H < 1 || W < 1 || H > kMaxExtent || W > kMaxExtent) return GSA_ERR_INVALID;
+    if (n < 0 || !extent_ok(H, W)) return GSA_ERR_INVALID;              // alone among the plane entries: H * W may reach 2^31
     if (n == 0) return GSA_OK;
     if (!mask || !out) return GSA_ERR_INVALID;
     const uint64_t bytes = (uint64_t)n * (uint64_t)H * (uint64_t)W;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(mask), b = reinterpret_cast<uintptr_t>(out);
-    if (a < b + bytes && b < a + bytes) return GSA_ERR_INVALID;        // the ranges overlap
-    const long long tiles_x = (W + kTileW - 1) / kTileW;
-    const long long tiles_per_plane = tiles_x * ((H + kTileH - 1) / kTileH);
-    if (tiles_per_plane * n >= kMaxTiles) return GSA_ERR_INVALID;
-    const bool aligned = W % 4 == 0 && ((a | b) & 3) == 0;
-    hipStream_t s = (hipStream_t)stream;
+    if (ranges_overlap(mask, bytes, out, bytes)) return GSA_ERR_INVALID;
+    const TileGrid g = tile_grid(H, W, kTileW, kTileH);
+    const long long tiles_per_plane = g.per_plane;
+    if (tiles_per_plane * n >= kMaxWorkgroups) return GSA_ERR_INVALID;  // refused, not split
+    const bool aligned = W % 4 == 0 && ((reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(out)) & 3) == 0;
     const dim3 grid((unsigned)(tiles_per_plane * n)), block(kThreads);
-    if (aligned)
-        hipLaunchKernelGGL(mask_morph_kernel<true>, grid, block, 0, s, mask, out, H, W, (int)tiles_x, (int)tiles_per_plane);
-    else
-        hipLaunchKernelGGL(mask_morph_kernel<false>, grid, block, 0, s, mask, out, H, W, (int)tiles_x, (int)tiles_per_plane);
+    const auto kernel = aligned ? mask_morph_kernel<true> : mask_morph_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, mask, out, H, W, (int)g.tiles_x, (int)tiles_per_plane);
     return hipGetLastError() == hipSuccess ? GSA_OK : GSA_ERR_HIP;
 }
 

@@ -24,6 +24,7 @@
 
 #include "../../include/gsa.h"
 #include "../../include/gsa_photometric.h"
+#include "gsa_plane.h"
 
 namespace {
 
@@ -236,8 +237,7 @@ int gsa_photometric(void* stream, int32_t n, int32_t H, int32_t W, int32_t chann
     if (!img || !params || !out || (reinterpret_cast<uintptr_t>(params) & 3)) return GSA_ERR_INVALID;
     const uint64_t row_bytes = (uint64_t)W * channels;
     const uint64_t total = (uint64_t)n * H * row_bytes;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(img), b = reinterpret_cast<uintptr_t>(out);
-    if (a < b + total && b < a + total) return GSA_ERR_INVALID;         // out is, or overlaps, img
+    if (gsa::plane::ranges_overlap(img, total, out, total)) return GSA_ERR_INVALID;     // out is, or overlaps, img
     const int64_t tiles_x = (int64_t)((row_bytes + kTileB - 1) / kTileB);
     const int64_t tiles_per_sample = tiles_x * ((H + kTileH - 1) / kTileH);
     if (tiles_per_sample * n > 0x7fffffffll) return GSA_ERR_INVALID;

@@ -26,8 +26,11 @@
 
 #include "../../include/gsa.h"
 #include "../../include/gsa_stats.h"
+#include "gsa_plane.h"
 
 namespace {
+
+using namespace gsa::plane;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -36,8 +39,6 @@ constexpr int kWaveRows = 8;                    // rows of a wave
 constexpr int kTileW = 256;                     // 64 lanes x kPix
 constexpr int kTileH = 32;                      // kWaves x kWaveRows
 constexpr int kSlots = GSA_STATS_SLOTS;
-constexpr int kMaxExtent = 65535;
-constexpr long long kMaxBlocks = (1ll << 24) - 1;      // HIP takes fewer than 2^32 threads per launch
 
 static_assert(kTileW == 64 * kPix && kTileH == kWaves * kWaveRows, "a lane per mask dword, a wave per row group");
 static_assert(kTileW * kTileH * 255ll * 255ll < (1ll << 31), "the 32-bit partials hold a tile");
@@ -81,14 +82,12 @@ __global__ __launch_bounds__(kThreads) void pair_stats_kernel(const uint8_t* __r
                                                               long long* __restrict__ rows, int H, int W, int tiles_x, int tiles_per_plane) {
     constexpr int CD = C ? C : 1;
     __shared__ int part[GSA_STATS_ROW];          // the workgroup's row: sums as 32-bit words, boxes as signed ints
-    const int plane = blockIdx.x / tiles_per_plane;                     // uniform over the workgroup
-    const int tile = blockIdx.x - plane * tiles_per_plane;
-    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
+    const Tile t = tile_of(tiles_x, tiles_per_plane);                   // uniform over the workgroup
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int xw = tile_x * kTileW, x = xw + lane * kPix;               // x < 65536 + 256
-    const int yb = tile_y * kTileH + wave * kWaveRows;
-    const uint8_t* __restrict__ pm = mask + (size_t)plane * H * W;     // every sample is a plane of its own
-    const uint8_t* __restrict__ pi = C ? img + (size_t)plane * H * W * C : nullptr;
+    const int xw = t.tile_x * kTileW, x = xw + lane * kPix;             // x < 65536 + 256
+    const int yb = t.tile_y * kTileH + wave * kWaveRows;
+    const uint8_t* __restrict__ pm = mask + (size_t)t.plane * H * W;   // every sample is a plane of its own
+    const uint8_t* __restrict__ pi = C ? img + (size_t)t.plane * H * W * C : nullptr;
 
     if (threadIdx.x < GSA_STATS_ROW) {
         const int f = threadIdx.x;
@@ -238,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void pair_stats_kernel(const uint8_t* __r
     // ---- the workgroup's row into the sample's: one 64-bit atomic per word that is not the identity
     if (threadIdx.x < GSA_STATS_RESERVED) {
         const int f = threadIdx.x;
-        long long* __restrict__ q = rows + (size_t)plane * GSA_STATS_ROW + f;
+        long long* __restrict__ q = rows + (size_t)t.plane * GSA_STATS_ROW + f;
         const int v = part[f];
         if (f >= GSA_STATS_BOX && f < GSA_STATS_CSUM) {
             if (part[GSA_STATS_COUNT + ((f - GSA_STATS_BOX) >> 2)] != 0) {
@@ -253,47 +252,33 @@ __global__ __launch_bounds__(kThreads) void pair_stats_kernel(const uint8_t* __r
     }
 }
 
-template <int C>
-void launch(hipStream_t s, bool aligned, unsigned blocks, const uint8_t* img, const uint8_t* mask, long long* rows, int H, int W,
-            int tiles_x, int tiles_per_plane) {
-    const dim3 grid(blocks), block(kThreads);
-    if (aligned)
-        hipLaunchKernelGGL((pair_stats_kernel<C, true>), grid, block, 0, s, img, mask, rows, H, W, tiles_x, tiles_per_plane);
-    else
-        hipLaunchKernelGGL((pair_stats_kernel<C, false>), grid, block, 0, s, img, mask, rows, H, W, tiles_x, tiles_per_plane);
-}
-
 }  // namespace
 
 extern "C" {
 
 int gsa_pair_stats(void* stream, int32_t n, int32_t H, int32_t W, int32_t C, const uint8_t* img, const uint8_t* mask, int64_t* rows) {
-    if (n < 0 || H < 1 || W < 1 || H > kMaxExtent || W > kMaxExtent || (long long)H * W >= (1ll << 31) || C < 0 || C > GSA_STATS_CHANNELS)
-        return GSA_ERR_INVALID;
+    if (n < 0 || !extent_ok_31(H, W) || C < 0 || C > GSA_STATS_CHANNELS) return GSA_ERR_INVALID;
     if (n == 0) return GSA_OK;
     if (!mask || !rows || (C > 0 && !img)) return GSA_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     long long* out = reinterpret_cast<long long*>(rows);
-    const int tiles_x = (W + kTileW - 1) / kTileW;
-    const int tiles_per_plane = tiles_x * ((H + kTileH - 1) / kTileH);                 // at most 2^18 + 2^11: H * W < 2^31
+    const TileGrid g = tile_grid(H, W, kTileW, kTileH);
+    const int tiles_x = (int)g.tiles_x, tiles_per_plane = (int)g.per_plane;             // at most 2^18 + 2^11: H * W < 2^31
     const bool aligned = W % 4 == 0 && ((reinterpret_cast<uintptr_t>(mask) | (C ? reinterpret_cast<uintptr_t>(img) : 0)) & 3) == 0;
-    const long long planes_per_launch = kMaxBlocks / tiles_per_plane;
-    for (long long first = 0; first < n; first += planes_per_launch) {
-        const long long planes = n - first < planes_per_launch ? n - first : planes_per_launch;
+    const auto kernel = C == 0   ? (aligned ? pair_stats_kernel<0, true> : pair_stats_kernel<0, false>)
+                        : C == 1 ? (aligned ? pair_stats_kernel<1, true> : pair_stats_kernel<1, false>)
+                        : C == 2 ? (aligned ? pair_stats_kernel<2, true> : pair_stats_kernel<2, false>)
+                        : C == 3 ? (aligned ? pair_stats_kernel<3, true> : pair_stats_kernel<3, false>)
+                                 : (aligned ? pair_stats_kernel<4, true> : pair_stats_kernel<4, false>);
+    for_each_launch(n, tiles_per_plane, [&](long long first, long long planes) {         // split, not refused
         const uint8_t* im = C ? img + (size_t)first * H * W * C : nullptr;
         const uint8_t* mk = mask + (size_t)first * H * W;
         long long* rw = out + first * GSA_STATS_ROW;
         const unsigned blocks = (unsigned)(planes * tiles_per_plane);
         const long long words = planes * GSA_STATS_ROW;                                 // fewer than 2^24 blocks as well
         hipLaunchKernelGGL(stats_init_kernel, dim3((unsigned)((words + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, rw, words, H, W);
-        switch (C) {
-            case 0: launch<0>(s, aligned, blocks, im, mk, rw, H, W, tiles_x, tiles_per_plane); break;
-            case 1: launch<1>(s, aligned, blocks, im, mk, rw, H, W, tiles_x, tiles_per_plane); break;
-            case 2: launch<2>(s, aligned, blocks, im, mk, rw, H, W, tiles_x, tiles_per_plane); break;
-            case 3: launch<3>(s, aligned, blocks, im, mk, rw, H, W, tiles_x, tiles_per_plane); break;
-            default: launch<4>(s, aligned, blocks, im, mk, rw, H, W, tiles_x, tiles_per_plane); break;
-        }
-    }
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kThreads), 0, s, im, mk, rw, H, W, tiles_x, tiles_per_plane);
+    });
     return hipGetLastError() == hipSuccess ? GSA_OK : GSA_ERR_HIP;
 }
 

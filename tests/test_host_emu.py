@@ -358,3 +358,47 @@ def test_photometric_behind_unaligned_addresses(programs, tmp_path, offsets):
     must stay inside the batch at both of its ends."""
     img = random_images(12, 3, 21, 30, 3)
     _photometric(programs, tmp_path, img, gpu_photometric._rows(3, 7, 1000), 7, 1000, offsets)
+
+
+# ---- the entry checks these units share (csrc/gsa_plane.h) -----------------------------------------------------------------------
+def _entry(programs, tmp_path, entry, n, H, W, nbytes, expect):
+    """One call that must end before the launch: `nbytes` of mask, outputs of the sizes that go with them, every output byte
+    still FILL afterwards."""
+    mask = np.zeros(nbytes, np.uint8)
+    if entry == "gsa_mask_morph":
+        scalars, tensors = (n, H, W), [("mask", "in", mask, 0), ("out", "out", nbytes, 0)]
+    else:
+        scalars, tensors = (n, H, W, 2, 255), [("mask", "in", mask, 0), ("dist2", "out", 2 * nbytes, 0), ("out", "out", nbytes, 0)]
+    got = run_case(programs, tmp_path, entry, scalars, tensors, expect=expect)
+    for name, part in got.items():
+        assert (part == FILL).all(), "%s n %d H %d W %d: %s was written to" % (entry, n, H, W, name)
+
+
+@pytest.mark.parametrize("entry", ["gsa_mask_morph", "gsa_mask_boundary"])
+def test_extents_past_65535_are_refused(programs, tmp_path, entry):
+    _entry(programs, tmp_path, entry, 1, 65536, 1, 65536, -1)
+    _entry(programs, tmp_path, entry, 1, 1, 65536, 65536, -1)
+
+
+def test_an_empty_batch_of_the_largest_planes_is_ok_and_writes_nothing(programs, tmp_path):
+    """n = 0 at the largest extents each entry takes.  gsa_mask_morph takes 65535 x 65535; gsa_mask_boundary keeps plane-local
+    indices in 32 bits and refuses H * W >= 2^31 whatever n is, so its largest plane here is 65535 x 32768 = 2^31 - 32768 pixels."""
+    _entry(programs, tmp_path, "gsa_mask_morph", 0, 65535, 65535, 8, 0)
+    _entry(programs, tmp_path, "gsa_mask_boundary", 0, 65535, 32768, 8, 0)
+    _entry(programs, tmp_path, "gsa_mask_boundary", 0, 65535, 65535, 8, -1)
+    _entry(programs, tmp_path, "gsa_mask_boundary", 0, 65535, 32769, 8, -1)
+
+
+def test_mask_morph_refuses_a_grid_of_2_to_the_24_tiles(programs, tmp_path):
+    """n = 2^24 planes of 1 x 1: one tile each, exactly the ceiling, 16 MiB per tensor -- refused (not split) before a byte is
+    written.  One plane fewer would be launched."""
+    _entry(programs, tmp_path, "gsa_mask_morph", 1 << 24, 1, 1, 1 << 24, -1)
+
+
+def test_photometric_refuses_a_plane_no_larger_than_its_blur_radius(programs, tmp_path):
+    """H = 3 = the blur radius: refused on shape grounds, as W = 3 is."""
+    for H, W in ((3, 8), (8, 3)):
+        img = random_images(1, 1, H, W, 3)
+        tensors = [("img", "in", img, 0), ("params", "in", gpu_photometric._rows(1, 7, 1000), 0), ("out", "out", img.size, 0)]
+        got = run_case(programs, tmp_path, "gsa_photometric", (1, H, W, 3, 7, 1000), tensors, expect=-1)
+        assert (got["out"] == FILL).all()
