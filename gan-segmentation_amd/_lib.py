@@ -127,9 +127,17 @@ SIGNATURES = {
     },
 }
 
+# The same rows for the entries whose header is not under include/ yet: path below the package -> {name: (result type, argument types)}.
+# tests/test_overlay_abi.py checks it against the header's text, as SIGNATURES is checked (DESIGN.md section 21 says why it is apart).
+EXTRA_SIGNATURES = {
+    "csrc/gsa_overlay.h": {
+        "gsa_overlay": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
+    },
+}
+
 
 class Api:
-    """Function table of one shared library: every entry of ``SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full name;
+    """Function table of one shared library: every entry of ``SIGNATURES`` and then of ``EXTRA_SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full name;
     the entries of include/gsa.h are attributes without the prefix as well (``api.create``, ``api.generate``, ...)."""
 
     def __init__(self, path, prefix="gsa_"):
@@ -143,7 +151,7 @@ class Api:
         import torch  # noqa: F401
         self.lib = ctypes.CDLL(path)
         self._fns = {}
-        for header, group in SIGNATURES.items():
+        for header, group in list(SIGNATURES.items()) + list(EXTRA_SIGNATURES.items()):
             for name, (res, args) in group.items():
                 try:
                     fn = getattr(self.lib, name)

@@ -14,6 +14,13 @@ pixel within r pixels of a pixel of another class, on both sides of every class 
 ``mask_*.png`` holds 255 there, the value the reference's dataset readers map to -1.  The additive key
 ``PAIR_STATS: true`` (default false) adds one ``pair_stats_<first>_<last + 1>.npz`` per rank with the per-sample statistics of the
 written pairs (``pair_stats.pair_stats``); ``python -m gan_segmentation_amd.pair_stats DIR`` merges them into a report.
+The additive key ``PREVIEW_EVERY: k`` (integer >= 0, default 0: off) also writes ``vis_%06d.jpg`` for every sample whose global
+index is a multiple of k: the mask of the pair as written (after downscale, morphology, area filter and ignore band) laid over its
+image in ``preview.DATASET_COLOURS`` at alpha 0.5 with solid class outlines (``preview.overlay``), box-filtered by the additive key
+``PREVIEW_DOWNSCALE: f`` (1, 2, 4, 8 or 16; default 1).  Which of them exist depends on the index only, not on the batch size or
+the number of ranks.  Previews are diagnostics, not part of the dataset contract: they are not byte-specified as files (PIL encodes
+them, at quality 95), and they are not withheld by the device check that withholds a bad batch's pair files.
+``python -m gan_segmentation_amd.preview DIR`` makes contact sheets of a written dataset from its files.
 With torchrun (one process per GPU) the sample indices are sharded across ranks and every rank
 writes its own files -- no collective is needed when the sink is the filesystem.
 """
@@ -63,6 +70,7 @@ def generate(cfg, limit=None, workers=None):
     from .dataset_writer import DatasetWriter, DeviceCheckFailed
     from .image_generator import ImageGenerator
     from .pair_stats import check_pair_stats
+    from .preview import check_preview_downscale, check_preview_every, write_previews
     from .seg_solver import SegSolver
     from .weights import GAN_MAX_RES_LOG2
 
@@ -88,6 +96,9 @@ def generate(cfg, limit=None, workers=None):
     mask_ignore_band = ImageGenerator.check_mask_ignore_band(cfg.get("MASK_IGNORE_BAND", 0))
     mask_ignore_label = ImageGenerator.check_mask_ignore_label(cfg.get("MASK_IGNORE_LABEL", 255))
     stats = check_pair_stats(cfg.get("PAIR_STATS", False))    # additive key, checked here as well: every rank writes its own shard file
+    # additive keys, checked here as well: vis_%06d.jpg for the samples whose index is a multiple of k (off by default)
+    preview_every = check_preview_every(cfg.get("PREVIEW_EVERY", 0))
+    preview_downscale = check_preview_downscale(cfg.get("PREVIEW_DOWNSCALE", 1))
 
     solver = SegSolver(GAN_MAX_RES_LOG2[gan], os.path.join(root_dir, "data"), os.path.join(root_dir, "checkpoints"),
                        gpu_ids=solver_ids, keep_weights=False, precision=precision)
@@ -116,6 +127,8 @@ def generate(cfg, limit=None, workers=None):
                 # the device-side checks travel with the batch: 8 bytes copied behind its kernels, read by the writer before it
                 # releases the batch's files -- a run of 10 000 samples stops at the first bad batch instead of reporting at close()
                 writer.submit(img, mask, index, status=netG.snapshot_status())
+                if preview_every:       # a diagnostic beside the writer, not through its ring: overlay on the device, PIL on this thread
+                    write_previews(dst_dir, img, mask, index, preview_every, preview_downscale)
     except DeviceCheckFailed as e:
         print("generate: %s" % e, file=sys.stderr)
         return -2
@@ -125,17 +138,28 @@ def generate(cfg, limit=None, workers=None):
 
 def export_for_annotation(cfg, count):
     """Headless stand-in for the sampling half of the annotator (reference seg_annotator.py:286-337): generate `count`
-    samples and save what the GUI saves next to a drawn mask -- BASE_DIR/data/img_%06d.jpg and feat_%06d.pickle."""
-    from . import annotation_io
+    samples and save what the GUI saves next to a drawn mask -- BASE_DIR/data/img_%06d.jpg and feat_%06d.pickle.  When a decoder
+    checkpoint exists, also vis_img_%06d.jpg, the reference's name and content (seg_annotator.py:330-346): the current decoder's
+    prediction over the image, ``preview.REFERENCE_COLOURS`` at alpha 0.5, background skipped, no outline."""
+    import torch
+    from . import annotation_io, preview
     from .image_generator import ImageGenerator
     gpu = list(cfg["GAN_GPU_IDS"])[0]
     netG = ImageGenerator(gpu_ids=[gpu], gan_dir=cfg["GAN_DIR"], gan=cfg["GAN"], batch_size=cfg["GAN_BATCH_SIZE_PER_GPU"],
                           precision=cfg.get("PRECISION", "fp32"), seed=int(cfg.get("SEED", 0)),
                           truncation_psi=cfg.get("TRUNCATION_PSI"))     # annotation samples are never style-mixed
     dst = os.path.join(cfg["BASE_DIR"], "data")
+    ckpt = os.path.join(cfg["BASE_DIR"], "checkpoints")
+    trained = os.path.isdir(ckpt) and any(os.path.splitext(f)[1] == ".params" for f in os.listdir(ckpt))     # SegSolver.load's test
+    solver = _solver(cfg, keep_weights=True) if trained else None       # without a checkpoint no decoder is created
+    lut = preview.make_lut(preview.REFERENCE_COLOURS, alpha=0.5, skip_background=True)
     for i, (img, feats) in enumerate(netG.get_images(count)):
         annotation_io.export_sample(dst, i, img, feats)
-    print("wrote %d samples (img + feat) to %s" % (count, dst))
+        if trained:                 # the reference's create_image_iterator / next_image: predict from the features, draw, save
+            mask = solver.predict(feats, keep_on_device=True)[..., 0].to(torch.uint8).contiguous()
+            vis = preview.overlay(torch.from_numpy(np.ascontiguousarray(img)).to(mask.device)[None], mask, lut)
+            preview.save_jpeg(os.path.join(dst, "vis_img_%06d.jpg" % i), vis[0].cpu().numpy())
+    print("wrote %d samples (img + feat%s) to %s" % (count, " + vis_img" if trained else "", dst))
     return 0
 
 
