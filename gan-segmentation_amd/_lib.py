@@ -135,9 +135,19 @@ EXTRA_SIGNATURES = {
     },
 }
 
+# The table that later features add their rows to: one key per header beside its unit, path below the package -> {name: (result
+# type, argument types)}, bound after the two tables above.  Each header has a test of its own that checks its row against the
+# header's text (tests/test_refine_abi.py for the first); no test pins this table's list of keys.  Folding all three tables into
+# include/ and SIGNATURES is the follow-up that edits the tests which pin those two.
+UNIT_SIGNATURES = {
+    "csrc/gsa_refine.h": {
+        "gsa_mask_refine": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    },
+}
+
 
 class Api:
-    """Function table of one shared library: every entry of ``SIGNATURES`` and then of ``EXTRA_SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full name;
+    """Function table of one shared library: every entry of ``SIGNATURES``, then of ``EXTRA_SIGNATURES``, then of ``UNIT_SIGNATURES``, bound once.  ``fn(name)`` returns an entry by its full name;
     the entries of include/gsa.h are attributes without the prefix as well (``api.create``, ``api.generate``, ...)."""
 
     def __init__(self, path, prefix="gsa_"):
@@ -151,7 +161,7 @@ class Api:
         import torch  # noqa: F401
         self.lib = ctypes.CDLL(path)
         self._fns = {}
-        for header, group in list(SIGNATURES.items()) + list(EXTRA_SIGNATURES.items()):
+        for header, group in list(SIGNATURES.items()) + list(EXTRA_SIGNATURES.items()) + list(UNIT_SIGNATURES.items()):
             for name, (res, args) in group.items():
                 try:
                     fn = getattr(self.lib, name)

@@ -24,7 +24,7 @@ def is_device_tensor(t, dtype, dims=None, shape=None, device=None):
 
 
 def launch(name, dev, *args):
-    """Call the stateless entry ``name`` (a row of ``_lib.SIGNATURES`` or ``_lib.EXTRA_SIGNATURES`` whose first argument is the stream) with ``args`` behind the current
+    """Call the stateless entry ``name`` (a row of ``_lib.SIGNATURES``, ``_lib.EXTRA_SIGNATURES`` or ``_lib.UNIT_SIGNATURES`` whose first argument is the stream) with ``args`` behind the current
     stream of ``dev``.  The C ABI has no context: its kernels go to the calling thread's current device, so ``dev`` is made
     that for the call.  GsaError on a non-zero status."""
     with torch.cuda.device(dev):

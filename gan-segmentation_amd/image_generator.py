@@ -39,6 +39,12 @@ consumers ignore: ``labels="int64"`` of the training stream maps it to -1, the p
 every fused call wherever a pixel of another value lies within r pixels -- ``mask_ops.ignore_band``, the rule of
 include/gsa_boundary.h, DESIGN.md section 18: a band on both sides of every class boundary, at the output resolution, applied
 LAST, after ``mask_morph`` and the component filter, and before anything reads the mask.  The image is untouched.
+
+``mask_refine=k`` (fixed at construction; 0, the default, is off; up to 8) runs k passes of ``mask_ops.refine`` on the mask of every
+fused call: a joint bilateral vote that moves the class boundaries onto the edges of the pair's own image (the rule of
+csrc/gsa_refine.h), with the weights of ``mask_refine_radius`` (3), ``mask_refine_sigma_space`` (2.0) and
+``mask_refine_sigma_colour`` (32.0) and the attached decoder's class count -- FIRST, on the pair as written (after
+``output_downscale``), before ``mask_morph``, the component filter and the band.  The image is read, never written.
 """
 import os
 
@@ -67,34 +73,39 @@ class ImageGenerator:
     mask_min_area = 0
     mask_connectivity = 8
     mask_fill = "neighbour"
+    mask_refine = 0
+    mask_refine_radius = 3
+    mask_refine_sigma_space = 2.0
+    mask_refine_sigma_colour = 32.0
     mask_ignore_band = 0
     mask_ignore_label = 255
 
     def __init__(self, gpu_ids, gan_dir, gan="ffhq", batch_size=4, return_latents=False, seed=0, precision="fp32",
                  truncation_psi=None, style_mix_prob=0.0, output_downscale=1, mask_morph=False, mask_min_area=0, mask_connectivity=8,
-                 mask_fill="neighbour", mask_ignore_band=0, mask_ignore_label=255):
+                 mask_fill="neighbour", mask_refine=0, mask_refine_radius=3, mask_refine_sigma_space=2.0, mask_refine_sigma_colour=32.0,
+                 mask_ignore_band=0, mask_ignore_label=255):
         cfg = self._get_config(max_res_log2=_weights.GAN_MAX_RES_LOG2[gan])
         self._setup(cfg, os.path.join(gan_dir, "stylegan-%s.params" % gan), gpu_ids, batch_size, return_latents, seed, precision,
                     truncation_psi, style_mix_prob, output_downscale, mask_morph, mask_min_area, mask_connectivity, mask_fill,
-                    mask_ignore_band, mask_ignore_label)
+                    mask_refine, mask_refine_radius, mask_refine_sigma_space, mask_refine_sigma_colour, mask_ignore_band, mask_ignore_label)
 
     @classmethod
     def from_params(cls, gcfg, gparams, dcfg=None, dparams=None, gpu_ids=(0,), batch_size=4,
                     return_latents=False, seed=0, precision="fp32", truncation_psi=None, style_mix_prob=0.0, output_downscale=1,
-                    mask_morph=False, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour", mask_ignore_band=0,
-                    mask_ignore_label=255):
+                    mask_morph=False, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour", mask_refine=0, mask_refine_radius=3,
+                    mask_refine_sigma_space=2.0, mask_refine_sigma_colour=32.0, mask_ignore_band=0, mask_ignore_label=255):
         """Build from in-memory weights (tests, benchmarks: no pretrained files exist here)."""
         self = cls.__new__(cls)
         self._setup(dict(gcfg), gparams, gpu_ids, batch_size, return_latents, seed, precision, truncation_psi, style_mix_prob,
                     output_downscale, mask_morph, mask_min_area, mask_connectivity, mask_fill,
-                    mask_ignore_band, mask_ignore_label)
+                    mask_refine, mask_refine_radius, mask_refine_sigma_space, mask_refine_sigma_colour, mask_ignore_band, mask_ignore_label)
         if dcfg is not None:
             self.attach_decoder(dcfg, dparams)
         return self
 
     def _setup(self, cfg, gparams, gpu_ids, batch_size, return_latents, seed, precision, truncation_psi, style_mix_prob,
-               output_downscale, mask_morph, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour", mask_ignore_band=0,
-               mask_ignore_label=255):
+               output_downscale, mask_morph, mask_min_area=0, mask_connectivity=8, mask_fill="neighbour", mask_refine=0,
+               mask_refine_radius=3, mask_refine_sigma_space=2.0, mask_refine_sigma_colour=32.0, mask_ignore_band=0, mask_ignore_label=255):
         """What both constructors do: the options, checked before any file or device is touched; one generator replica per gpu
         id, loaded from ``gparams`` (a ``.params`` path, read once, or a ``{name: array}`` dict); the seeds."""
         self.cfg = cfg
@@ -104,6 +115,10 @@ class ImageGenerator:
         self.mask_min_area = self.check_mask_min_area(mask_min_area)
         self.mask_connectivity = self.check_mask_connectivity(mask_connectivity)
         self.mask_fill = self.check_mask_fill(mask_fill)
+        self.mask_refine = self.check_mask_refine(mask_refine)
+        self.mask_refine_radius = self.check_mask_refine_radius(mask_refine_radius)
+        self.mask_refine_sigma_space = self.check_mask_refine_sigma_space(mask_refine_sigma_space)
+        self.mask_refine_sigma_colour = self.check_mask_refine_sigma_colour(mask_refine_sigma_colour)
         self.mask_ignore_band = self.check_mask_ignore_band(mask_ignore_band)
         self.mask_ignore_label = self.check_mask_ignore_label(mask_ignore_label)
         self.latent_size = cfg["latent_size"]
@@ -172,6 +187,26 @@ class ImageGenerator:
     def check_mask_fill(v):
         """What the component filter writes into a small component: "neighbour" or an int 0..255 (ValueError otherwise)."""
         return "neighbour" if _mask_ops.check_fill(v, "mask_fill") == _mask_ops.FILL_NEIGHBOUR else int(v)
+
+    @staticmethod
+    def check_mask_refine(v):
+        """The number of refinement passes as an int: 0 .. 8, 0 meaning off (ValueError otherwise)."""
+        return _mask_ops.check_refine_iterations(v, "mask_refine")
+
+    @staticmethod
+    def check_mask_refine_radius(v):
+        """The window radius of the refinement as an int: 1 .. 5 (ValueError otherwise)."""
+        return _mask_ops.check_refine_radius(v, "mask_refine_radius")
+
+    @staticmethod
+    def check_mask_refine_sigma_space(v):
+        """The spatial width of the refinement's weights in pixels as a float > 0 (ValueError otherwise)."""
+        return _mask_ops.check_refine_sigma(v, "mask_refine_sigma_space")
+
+    @staticmethod
+    def check_mask_refine_sigma_colour(v):
+        """The colour width of the refinement's weights, in summed absolute channel differences, as a float > 0 (ValueError otherwise)."""
+        return _mask_ops.check_refine_sigma(v, "mask_refine_sigma_colour")
 
     @staticmethod
     def check_mask_ignore_band(v):
@@ -379,8 +414,8 @@ class ImageGenerator:
 
     def _pair_buffers(self, r, n, out):
         """(img, raw mask, final mask) of a fused step of ``n`` samples on replica ``r``: new tensors, or the checked ``out``; the
-        step writes the raw mask, ``_finish_mask`` turns it into the final one (the same tensor without ``mask_morph``,
-        ``mask_min_area`` and ``mask_ignore_band``)."""
+        step writes the raw mask, ``_finish_mask`` turns it into the final one (the same tensor without ``mask_refine``,
+        ``mask_morph``, ``mask_min_area`` and ``mask_ignore_band``)."""
         g = self._gens[r]
         dev = g._model.device
         if out is None:
@@ -397,13 +432,13 @@ class ImageGenerator:
         z, noise, n = g._prepare(z, noise)
         img, raw, final = self._pair_buffers(r, n, out)
         self._run_step(g._model, g._model.device, n, z, [a.data_ptr() for a in noise], img, raw)
-        return img, self._finish_mask(r, raw, final)
+        return img, self._finish_mask(r, raw, final, img)
 
     def _raw_mask(self, r, mask):
-        """Where the step of replica ``r`` writes its mask: ``mask`` itself, or with ``mask_morph``, ``mask_min_area`` or
-        ``mask_ignore_band`` a scratch tensor kept per replica, batch size and stream (calls on one stream are ordered, so they may
+        """Where the step of replica ``r`` writes its mask: ``mask`` itself, or with ``mask_refine``, ``mask_morph``, ``mask_min_area``
+        or ``mask_ignore_band`` a scratch tensor kept per replica, batch size and stream (calls on one stream are ordered, so they may
         share it) -- the same address every call, so a captured graph that bakes it in stays valid whatever ``mask`` is."""
-        if not self.mask_morph and self.mask_min_area <= 1 and not self.mask_ignore_band:
+        if not self.mask_refine and not self.mask_morph and self.mask_min_area <= 1 and not self.mask_ignore_band:
             return mask
         return self._mask_scratch("raw", r, mask, torch.uint8)
 
@@ -416,9 +451,14 @@ class ImageGenerator:
             t = cache[key] = torch.empty(mask.shape, dtype=dtype, device=mask.device)
         return t
 
-    def _finish_mask(self, r, raw, final):
-        """The mask a fused call of replica ``r`` returns: the raw one passed through ``mask_morph``, then through the component
-        filter of ``mask_min_area`` and last through the ignore band of ``mask_ignore_band``, whichever are on --
+    def _refine_classes(self):
+        """K of the refinement: the class count of the attached decoder, its last feature count (2..8; ValueError otherwise)."""
+        return _mask_ops.check_refine_classes(int(self._decoder.cfg["features"][-1]), "the attached decoder's class count")
+
+    def _finish_mask(self, r, raw, final, img):
+        """The mask a fused call of replica ``r`` returns: the raw one passed through the ``mask_refine`` passes of the image-guided
+        vote against ``img``, the pair's image as written, then through ``mask_morph``, then through the component filter of
+        ``mask_min_area`` and last through the ignore band of ``mask_ignore_band``, whichever are on --
         eager launches behind the step on the same stream (never part of a captured graph), before anything reads the mask.  The
         filter's labels and areas (int32 each: 8 bytes per pixel, 256 MiB for ffhq at batch 32) and the masks between two stages
         are scratch of the same kind as the raw mask."""
@@ -429,6 +469,11 @@ class ImageGenerator:
         def target(what, last):
             # a stage writes the final mask if it is the last one that is on, a scratch tensor of its own otherwise
             return final if last else self._mask_scratch(what, r, final, torch.uint8)
+        if self.mask_refine:
+            raw = _mask_ops.refine(img, raw, self.mask_refine, self.mask_refine_radius, self._refine_classes(),
+                                   sigma_space=self.mask_refine_sigma_space, sigma_colour=self.mask_refine_sigma_colour,
+                                   out=target("refined", not self.mask_morph and not filtered and not banded),
+                                   scratch=self._mask_scratch("refining", r, final, torch.uint8) if self.mask_refine > 1 else None)
         if self.mask_morph:
             raw = _mask_ops.morph_mask(raw, out=target("morphed", not filtered and not banded))
         if filtered:
@@ -493,7 +538,7 @@ class ImageGenerator:
         img, raw, final = self._pair_buffers(r, n, out)
         self._step(g._model.ctx, current_stream_ptr(g._model.device), n, None, [a.data_ptr() for a in noise], img, raw,
                    self.output_downscale, dl, g.num_style_layers)
-        return img, self._finish_mask(r, raw, final)
+        return img, self._finish_mask(r, raw, final, img)
 
     @staticmethod
     def _capture(model, dev, n, z, nptrs, img, mask, factor=1):

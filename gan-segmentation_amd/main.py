@@ -11,7 +11,10 @@ the GPU with the 5x5 close + open of reference utils.morph_mask before it is wri
 0..255) replace every connected component of fewer than k pixels, after the morphology (``mask_ops.despeckle``).  The additive keys
 ``MASK_IGNORE_BAND: r`` (0..32 px, default 0: off) and ``MASK_IGNORE_LABEL`` (0..255, default 255) then write the label into every
 pixel within r pixels of a pixel of another class, on both sides of every class boundary (``mask_ops.ignore_band``): the stored
-``mask_*.png`` holds 255 there, the value the reference's dataset readers map to -1.  The additive key
+``mask_*.png`` holds 255 there, the value the reference's dataset readers map to -1.  The additive keys ``MASK_REFINE: k`` (0..8 passes, default 0: off),
+``MASK_REFINE_RADIUS`` (1..5, default 3), ``MASK_REFINE_SIGMA_SPACE`` (default 2.0) and ``MASK_REFINE_SIGMA_COLOUR`` (default 32.0, in
+summed absolute channel differences) run an image-guided vote on every mask BEFORE all of the above (``mask_ops.refine``): a pixel
+takes the class that its neighbours of similar colour in the pair's own image agree on.  The additive key
 ``PAIR_STATS: true`` (default false) adds one ``pair_stats_<first>_<last + 1>.npz`` per rank with the per-sample statistics of the
 written pairs (``pair_stats.pair_stats``); ``python -m gan_segmentation_amd.pair_stats DIR`` merges them into a report.
 The additive key ``PREVIEW_EVERY: k`` (integer >= 0, default 0: off) also writes ``vis_%06d.jpg`` for every sample whose global
@@ -95,6 +98,11 @@ def generate(cfg, limit=None, workers=None):
     # additive keys, checked here as well: the ignore band around class boundaries (off by default), applied last
     mask_ignore_band = ImageGenerator.check_mask_ignore_band(cfg.get("MASK_IGNORE_BAND", 0))
     mask_ignore_label = ImageGenerator.check_mask_ignore_label(cfg.get("MASK_IGNORE_LABEL", 255))
+    # additive keys, checked here as well: the image-guided refinement of the mask (off by default), applied first
+    mask_refine = ImageGenerator.check_mask_refine(cfg.get("MASK_REFINE", 0))
+    mask_refine_radius = ImageGenerator.check_mask_refine_radius(cfg.get("MASK_REFINE_RADIUS", 3))
+    mask_refine_sigma_space = ImageGenerator.check_mask_refine_sigma_space(cfg.get("MASK_REFINE_SIGMA_SPACE", 2.0))
+    mask_refine_sigma_colour = ImageGenerator.check_mask_refine_sigma_colour(cfg.get("MASK_REFINE_SIGMA_COLOUR", 32.0))
     stats = check_pair_stats(cfg.get("PAIR_STATS", False))    # additive key, checked here as well: every rank writes its own shard file
     # additive keys, checked here as well: vis_%06d.jpg for the samples whose index is a multiple of k (off by default)
     preview_every = check_preview_every(cfg.get("PREVIEW_EVERY", 0))
@@ -108,6 +116,8 @@ def generate(cfg, limit=None, workers=None):
     netG = ImageGenerator(gpu_ids=gan_ids, gan_dir=gan_dir, gan=gan, batch_size=batch, precision=precision,
                           truncation_psi=truncation_psi, style_mix_prob=style_mix_prob, output_downscale=downscale,
                           mask_morph=mask_morph, mask_min_area=mask_min_area, mask_connectivity=mask_connectivity, mask_fill=mask_fill,
+                          mask_refine=mask_refine, mask_refine_radius=mask_refine_radius, mask_refine_sigma_space=mask_refine_sigma_space,
+                          mask_refine_sigma_colour=mask_refine_sigma_colour,
                           mask_ignore_band=mask_ignore_band, mask_ignore_label=mask_ignore_label)
     netG.attach_decoder(solver.cfg, solver.net)
     dst_dir = os.path.join(root_dir, "dataset", "train_generated")

@@ -14,7 +14,12 @@ And the binding of the boundary distance (include/gsa_boundary.h, csrc/gsa_bound
 reference does not have either: ``boundary_distance(mask)`` gives every pixel's squared Euclidean distance to the nearest pixel of
 another value, up to a radius; ``ignore_band(mask, radius)`` writes a label (255, the value the consumers ignore) wherever that
 distance is at most ``radius``^2 -- VOC's void border, on both sides of every class boundary; ``ImageGenerator(...,
-mask_ignore_band=r)`` applies it to the mask of every fused call, last."""
+mask_ignore_band=r)`` applies it to the mask of every fused call, last.
+
+And the binding of the image-guided refinement (csrc/gsa_refine.h, csrc/gsa_refine.hip), the one operator here
+that looks at the pair's image: ``refine(img, mask)`` gives every pixel the class its neighbours of similar colour agree on -- a
+joint bilateral vote, in integers, with the weights of ``refine_tables``; ``ImageGenerator(..., mask_refine=k)`` applies k passes of
+it to the mask of every fused call, FIRST."""
 import numpy as np
 import torch
 
@@ -37,6 +42,12 @@ MAX_AREA = 2 ** 31 - 1
 # include/gsa_boundary.h
 BOUNDARY_FAR = 32767        # dist2 of a pixel with no other value within the radius
 BOUNDARY_MAX_RADIUS = 32
+
+# csrc/gsa_refine.h
+REFINE_MAX_RADIUS = 5
+REFINE_MAX_CLASSES = 8
+REFINE_MAX_ITERATIONS = 8
+REFINE_TABLE_BYTES = 256 + 11 * 11
 
 
 def _check(t, what):
@@ -213,3 +224,112 @@ def ignore_band(mask, radius, label=255, out=None, return_distance=False):
         launch("gsa_mask_boundary", mask.device, n, H, W, radius, label, mask.data_ptr(), dist2.data_ptr() if return_distance else None,
                out.data_ptr())
     return (out, dist2) if return_distance else out
+
+
+def check_refine_iterations(v, what="iterations"):
+    """A number of refinement passes as an int: 0 .. 8, 0 meaning off (only the ``ImageGenerator`` keyword and the config key take it;
+    ``refine`` wants 1 .. 8).  ValueError otherwise; a bool is not a number here."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= REFINE_MAX_ITERATIONS:
+        raise ValueError("%s must be an int in 0..%d, got %r" % (what, REFINE_MAX_ITERATIONS, v))
+    return int(v)
+
+
+def check_refine_radius(v, what="radius"):
+    """The window radius of the vote as an int: 1 .. 5.  ValueError otherwise."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= REFINE_MAX_RADIUS:
+        raise ValueError("%s must be an int in 1..%d, got %r" % (what, REFINE_MAX_RADIUS, v))
+    return int(v)
+
+
+def check_refine_classes(v, what="classes"):
+    """The class count K of the vote as an int: 2 .. 8; mask values >= K are frozen.  ValueError otherwise."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 2 <= int(v) <= REFINE_MAX_CLASSES:
+        raise ValueError("%s must be an int in 2..%d, got %r" % (what, REFINE_MAX_CLASSES, v))
+    return int(v)
+
+
+def check_refine_sigma(v, what="sigma"):
+    """A width of the vote's weights as a float: finite and > 0.  ValueError otherwise; a bool is not a number here."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not float(v) > 0.0:
+        raise ValueError("%s must be a finite number > 0, got %r" % (what, v))
+    return float(v)
+
+
+def refine_tables(radius=3, sigma_space=2.0, sigma_colour=32.0):
+    """The weights of the vote as the C entry reads them: a numpy (377,) uint8 array, ``wr[256]`` then ``ws[11][11]`` row-major with the
+    entry of the offset (dy, dx) at ``(dy + 5) * 11 + (dx + 5)``, computed in float64:
+
+        wr[d]      = rint(255 * exp(-d^2 / (2 * sigma_colour^2)))
+        ws[dy][dx] = max(1, rint(255 * exp(-(dx^2 + dy^2) / (2 * sigma_space^2))))  inside the radius, 0 outside
+
+    ``d`` is the SUM over the channels of the absolute differences of two pixels, clamped to 255 -- not a Euclidean norm and not a
+    mean: for an RGB pair it is up to three times a per-channel difference, and ``sigma_colour`` is in those units."""
+    radius = check_refine_radius(radius)
+    sigma_space, sigma_colour = check_refine_sigma(sigma_space, "sigma_space"), check_refine_sigma(sigma_colour, "sigma_colour")
+    d = np.arange(256, dtype=np.float64)
+    wr = np.rint(255.0 * np.exp(-d * d / (2.0 * sigma_colour * sigma_colour)))
+    o = np.arange(-REFINE_MAX_RADIUS, REFINE_MAX_RADIUS + 1, dtype=np.float64)
+    ws = np.maximum(1.0, np.rint(255.0 * np.exp(-(o[:, None] ** 2 + o[None, :] ** 2) / (2.0 * sigma_space * sigma_space))))
+    ws[(np.abs(o)[:, None] > radius) | (np.abs(o)[None, :] > radius)] = 0.0
+    return np.concatenate([wr, ws.reshape(-1)]).astype(np.uint8)
+
+
+_device_tables = {}
+
+
+def _tables_on(tables, device, radius, sigma_space, sigma_colour):
+    """The 377 weights as a uint8 tensor on ``device``: a device tensor is checked; a numpy table, or the one of the parameters, is
+    uploaded once per device and content."""
+    if isinstance(tables, torch.Tensor):
+        if not is_device_tensor(tables, torch.uint8, shape=(REFINE_TABLE_BYTES,), device=device):
+            raise ValueError("tables must be a contiguous uint8 tensor (%d,) on %s" % (REFINE_TABLE_BYTES, device))
+        return tables
+    if tables is None:
+        key = (str(device), radius, sigma_space, sigma_colour)
+    else:
+        tables = np.ascontiguousarray(tables)
+        if tables.shape != (REFINE_TABLE_BYTES,) or tables.dtype != np.uint8:
+            raise ValueError("tables must be a (%d,) uint8 array (refine_tables), got %s %s" % (REFINE_TABLE_BYTES, tables.shape, tables.dtype))
+        key = (str(device), tables.tobytes())
+    if key not in _device_tables:
+        host = refine_tables(radius, sigma_space, sigma_colour) if tables is None else tables.copy()
+        _device_tables[key] = torch.from_numpy(host).to(device)
+    return _device_tables[key]
+
+
+def refine(img, mask, iterations=1, radius=3, classes=8, tables=None, sigma_space=2.0, sigma_colour=32.0, out=None, scratch=None):
+    """img (H, W, C) or (n, H, W, C) and mask (H, W) or (n, H, W), contiguous uint8 CUDA tensors of one pair batch, C in 1..4 -> a
+    tensor of ``mask``'s shape (new, or ``out``, which must not overlap ``mask``): ``iterations`` (1..8) passes of the joint
+    bilateral vote of csrc/gsa_refine.h.  In a pass every pixel whose value is below ``classes`` (2..8) takes the class with the
+    largest sum of ``ws[dy][dx] * wr[d]`` over the pixels of its (2 * ``radius`` + 1)^2 window (``radius`` 1..5) that lie in the same
+    image and hold a class, ``d`` being the summed absolute colour difference to the pixel itself; it keeps its own value on a tie
+    with it, and takes the smallest class on any other tie.  Values >= ``classes`` -- the ignore label 255 -- stay and cast no vote.
+
+    ``tables``: the 377 weights (``refine_tables``) as a numpy array or a device tensor; None takes those of ``radius``,
+    ``sigma_space`` and ``sigma_colour``.  A numpy table is uploaded once per device.  ``scratch``: a uint8 tensor of ``mask``'s shape
+    for the passes before the last to alternate with ``out`` (the last pass writes ``out``) instead of a new one; it must overlap
+    neither ``mask`` nor ``out``.  Enqueued on the current stream of ``mask``'s device; ``img`` and ``mask`` are not written.
+    ValueError on anything else; no CPU fallback."""
+    n, H, W = _plane_shape(mask, "refine")
+    if not is_device_tensor(img, torch.uint8, dims=(mask.dim() + 1,), device=mask.device) or tuple(img.shape[:-1]) != tuple(mask.shape) \
+            or not 1 <= img.shape[-1] <= 4:
+        raise ValueError("img must be a contiguous uint8 tensor %s + (C,) with C in 1..4 on %s" % (tuple(mask.shape), mask.device))
+    iterations = check_refine_iterations(iterations)
+    if iterations == 0:
+        raise ValueError("iterations must be an int in 1..%d, got %r" % (REFINE_MAX_ITERATIONS, iterations))
+    radius, classes = check_refine_radius(radius), check_refine_classes(classes)
+    if tables is None:
+        sigma_space, sigma_colour = check_refine_sigma(sigma_space, "sigma_space"), check_refine_sigma(sigma_colour, "sigma_colour")
+    dev_tables = _tables_on(tables, mask.device, radius, sigma_space, sigma_colour)
+    out = torch.empty_like(mask) if out is None else _other_tensor(out, "out", torch.uint8, mask)
+    if iterations > 1:
+        scratch = torch.empty_like(mask) if scratch is None else _other_tensor(scratch, "scratch", torch.uint8, mask)
+        _other_tensor(scratch, "scratch", torch.uint8, out)
+    src = mask
+    for i in range(iterations):
+        dst = out if (iterations - 1 - i) % 2 == 0 else scratch
+        if n:
+            launch("gsa_mask_refine", mask.device, n, H, W, img.shape[-1], classes, radius, img.data_ptr(), src.data_ptr(),
+                   dev_tables.data_ptr(), dst.data_ptr())
+        src = dst
+    return out

@@ -10,7 +10,8 @@
 // A case is a text header and the input bytes:
 //
 //   gsa-emu-case 1
-//   entry gsa_mask_morph            one of the four entries below (five with -DGSA_EMU_OVERLAY and csrc/gsa_overlay.hip: gsa_overlay)
+//   entry gsa_mask_morph            one of the four entries below (with -DGSA_EMU_OVERLAY and csrc/gsa_overlay.hip also gsa_overlay; with
+//                                   -DGSA_EMU_REFINE and csrc/gsa_refine.hip also gsa_mask_refine; either without the other)
 //   expect 0                        the status the entry must return
 //   scalars 3 2 15 20               a count and the entry's integer arguments in order (decimal; 64-bit ones too)
 //   tensors 2                       a count and one line per pointer argument, in order:
@@ -38,6 +39,9 @@
 #include "../../include/gsa_photometric.h"
 #ifdef GSA_EMU_OVERLAY      // tests/test_host_emu_overlay.py: a fifth unit, gsa_overlay.hip, linked in
 #include "../../gan-segmentation_amd/csrc/gsa_overlay.h"
+#endif
+#ifdef GSA_EMU_REFINE       // tests/test_host_emu_refine.py: gsa_refine.hip linked in, with or without the overlay
+#include "../../gan-segmentation_amd/csrc/gsa_refine.h"
 #endif
 
 namespace {
@@ -114,6 +118,11 @@ int main(int argc, char** argv) {
     } else if (entry == "gsa_overlay") {
         need(6, 4);     // n H W channels factor cols; img mask lut out
         status = gsa_overlay(nullptr, i32(0), i32(1), i32(2), i32(3), t[0].at(), t[1].at(), t[2].at(), i32(4), i32(5), t[3].at());
+#endif
+#ifdef GSA_EMU_REFINE
+    } else if (entry == "gsa_mask_refine") {
+        need(6, 4);     // n H W channels classes radius; img mask tables out
+        status = gsa_mask_refine(nullptr, i32(0), i32(1), i32(2), i32(3), i32(4), i32(5), t[0].at(), t[1].at(), t[2].at(), t[3].at());
 #endif
     } else {
         malformed("unknown entry");
