@@ -143,6 +143,9 @@ UNIT_SIGNATURES = {
     "csrc/gsa_refine.h": {
         "gsa_mask_refine": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     },
+    "csrc/gsa_compare.h": {
+        "gsa_mask_compare": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    },
 }
 
 

@@ -24,6 +24,11 @@ image in ``preview.DATASET_COLOURS`` at alpha 0.5 with solid class outlines (``p
 the number of ranks.  Previews are diagnostics, not part of the dataset contract: they are not byte-specified as files (PIL encodes
 them, at quality 95), and they are not withheld by the device check that withholds a bad batch's pair files.
 ``python -m gan_segmentation_amd.preview DIR`` makes contact sheets of a written dataset from its files.
+`evaluate` takes the additive key ``EVAL_MASK_CHAINS`` (a mapping: chain name -> mapping of ``mask_ops.apply_filters`` keywords such as
+``morph: true`` or ``ignore_band: 2``, empty for the raw mask; absent by default: the reference's one line and nothing else) and prints
+one more line per chain: accuracy, mean-iou, band-accuracy, boundary-iou, abstained and changed of the decoder's mask passed through
+that chain, against the annotations under BASE_DIR/eval (``SegSolver.evaluate_masks``); the additive key ``EVAL_BAND`` (0..32 px,
+default 2) is the radius of the boundary band the two boundary figures are taken in.
 With torchrun (one process per GPU) the sample indices are sharded across ranks and every rank
 writes its own files -- no collective is needed when the sink is the filesystem.
 """
@@ -190,14 +195,45 @@ def train(cfg, epochs=None):
     return 0
 
 
+def check_eval_mask_chains(v):
+    """The EVAL_MASK_CHAINS key: None (absent), or a non-empty mapping of a name to a mapping of ``mask_ops.apply_filters`` keywords
+    (None for none: the raw mask) -> None or {name: complete keyword dict}.  ValueError otherwise."""
+    from . import mask_ops
+    if v is None:
+        return None
+    if not isinstance(v, dict) or not v:
+        raise ValueError("EVAL_MASK_CHAINS must be a mapping: chain name -> mapping of apply_filters keywords, got %r" % (v,))
+    chains = {}
+    for name, kw in v.items():
+        kw = {} if kw is None else kw
+        if not isinstance(name, str) or not isinstance(kw, dict) or not all(isinstance(k, str) for k in kw):
+            raise ValueError("EVAL_MASK_CHAINS: chain %r must be a mapping of apply_filters keywords, got %r" % (name, kw))
+        chains[name] = mask_ops.check_filters("EVAL_MASK_CHAINS: chain %r" % (name,), **kw)
+    return chains
+
+
+def check_eval_band(v):
+    """The EVAL_BAND key: the radius of the boundary band of the chain report as an int, 0 .. 32 px (ValueError otherwise)."""
+    from . import mask_ops
+    return mask_ops.check_band(v, "EVAL_BAND")
+
+
 def evaluate(cfg):
-    """The `evaluate` action (reference main.py:61-73) over BASE_DIR/eval."""
+    """The `evaluate` action (reference main.py:61-73) over BASE_DIR/eval.  With the additive key ``EVAL_MASK_CHAINS`` one more line
+    per chain: the decoder's mask through that filter chain against the annotations (``SegSolver.evaluate_masks``)."""
+    # additive keys, checked before any model is loaded
+    chains = check_eval_mask_chains(cfg.get("EVAL_MASK_CHAINS"))
+    band = check_eval_band(cfg.get("EVAL_BAND", 2))
     solver = _solver(cfg)
     if not solver.is_trained:
         print("train Decoder first!")
         return -1
-    result = solver.evaluate(os.path.join(cfg["BASE_DIR"], "eval"))
+    eval_dir = os.path.join(cfg["BASE_DIR"], "eval")
+    result = solver.evaluate(eval_dir)
     print(", ".join("%s: %.4f" % (name, value) for name, value in result))
+    if chains is not None:
+        for chain, values in solver.evaluate_masks(eval_dir, chains, band=band).items():
+            print("%s: %s" % (chain, ", ".join("%s: %.4f" % (name, value) for name, value in values)))
     return 0
 
 

@@ -19,7 +19,13 @@ mask_ignore_band=r)`` applies it to the mask of every fused call, last.
 And the binding of the image-guided refinement (csrc/gsa_refine.h, csrc/gsa_refine.hip), the one operator here
 that looks at the pair's image: ``refine(img, mask)`` gives every pixel the class its neighbours of similar colour agree on -- a
 joint bilateral vote, in integers, with the weights of ``refine_tables``; ``ImageGenerator(..., mask_refine=k)`` applies k passes of
-it to the mask of every fused call, FIRST."""
+it to the mask of every fused call, FIRST.
+
+And the binding of the mask agreement (csrc/gsa_compare.h, csrc/gsa_compare.hip), the one operator here that
+takes TWO masks: ``compare(pred, target, band)`` counts per sample the pixels of every (band code, target slot, prediction slot)
+combination -- the table ``metrics.MaskAgreement`` reads accuracy, mIoU, trimap accuracy and boundary IoU from.
+``apply_filters(img, mask, classes, ...)`` is the clean-up chain of ``ImageGenerator`` as a free function on any pair, so that a
+chain can be held against an annotation before a dataset run (``SegSolver.evaluate_masks``)."""
 import numpy as np
 import torch
 
@@ -48,6 +54,11 @@ REFINE_MAX_RADIUS = 5
 REFINE_MAX_CLASSES = 8
 REFINE_MAX_ITERATIONS = 8
 REFINE_TABLE_BYTES = 256 + 11 * 11
+
+# csrc/gsa_compare.h: word f * 81 + slot(target) * 9 + slot(pred) of a row, f = (in the target's band) + 2 * (in the prediction's)
+COMPARE_SLOTS = 9
+COMPARE_BANDS = 4
+COMPARE_ROW = COMPARE_BANDS * COMPARE_SLOTS * COMPARE_SLOTS
 
 
 def _check(t, what):
@@ -333,3 +344,101 @@ def refine(img, mask, iterations=1, radius=3, classes=8, tables=None, sigma_spac
                    dev_tables.data_ptr(), dst.data_ptr())
         src = dst
     return out
+
+
+def _overlaps(a, b):
+    """Whether the memory of two tensors overlaps (an empty one overlaps nothing)."""
+    pa, pb, sa, sb = a.data_ptr(), b.data_ptr(), a.numel() * a.element_size(), b.numel() * b.element_size()
+    return bool(sa and sb and pa < pb + sb and pb < pa + sa)
+
+
+def compare(pred, target, band=0, out=None, scratch=None):
+    """pred and target (H, W) or (n, H, W), contiguous uint8 CUDA tensors of equal shape on one device -> an int64 tensor
+    (n, COMPARE_ROW) on that device ((COMPARE_ROW,) for 2-D masks; new, or ``out``): per sample the number of pixels of every
+    combination of band code, target value and predicted value (the rule of csrc/gsa_compare.h).  Word ``f * 81 + slot(target) * 9 +
+    slot(pred)`` with ``slot(v) = min(v, 8)`` -- the values 0..7 each, everything from 8 up together, the ignore label 255 included
+    -- and ``f = (the pixel lies in target's band) + 2 * (it lies in pred's band)``.  A mask's band is what ``ignore_band(mask,
+    band)`` would overwrite: the pixels within ``band`` px, Euclidean, of a pixel of another value of the same mask; image edges make
+    no band.  ``band`` is 0..32; with 0 no band is computed and ``f`` is 0 everywhere, so the words from 81 on are zero.  With
+    ``band > 0`` ``boundary_distance(.., max_radius=band)`` runs on both masks first, into ``scratch`` (two int16 tensors of the masks'
+    shape: target's distances, then pred's) when given.  The 324 words of a sample sum to H * W; every word of the result is
+    overwritten.  ``rows.view(-1, 4, 9, 9)`` indexes it as [band code, target slot, prediction slot]; ``metrics.MaskAgreement`` turns
+    it into accuracy, mIoU, trimap accuracy and boundary IoU.  Enqueued on the current stream of the masks' device; the inputs are
+    not written.  ValueError on anything else; no CPU fallback."""
+    n, H, W = _plane_shape(pred, "compare")
+    if not is_device_tensor(target, torch.uint8, shape=pred.shape, device=pred.device):
+        raise ValueError("target must be a contiguous uint8 tensor %s on %s, as pred is" % (tuple(pred.shape), pred.device))
+    band = check_band(band, "band")
+    shapes = ((n, COMPARE_ROW),) if pred.dim() == 3 else ((1, COMPARE_ROW), (COMPARE_ROW,))
+    if out is None:
+        out = torch.empty((n, COMPARE_ROW), dtype=torch.int64, device=pred.device)
+    elif not is_device_tensor(out, torch.int64, device=pred.device) or tuple(out.shape) not in shapes:
+        raise ValueError("out must be a contiguous int64 tensor %s on %s" % (" or ".join(str(s) for s in shapes), pred.device))
+    elif _overlaps(out, pred) or _overlaps(out, target):
+        raise ValueError("out must not overlap pred or target")
+    dist = (None, None)
+    if scratch is not None:
+        if not isinstance(scratch, (tuple, list)) or len(scratch) != 2 or \
+                not all(is_device_tensor(t, torch.int16, shape=pred.shape, device=pred.device) for t in scratch):
+            raise ValueError("scratch must be two contiguous int16 tensors %s on %s" % (tuple(pred.shape), pred.device))
+        if _overlaps(scratch[0], scratch[1]) or any(_overlaps(t, o) for t in scratch for o in (pred, target, out)):
+            raise ValueError("scratch must be two different tensors that overlap neither mask nor out")
+    if band:
+        dist = (boundary_distance(target, band, out=None if scratch is None else scratch[0]),
+                boundary_distance(pred, band, out=None if scratch is None else scratch[1]))
+    if n:
+        launch("gsa_mask_compare", pred.device, n, H, W, band, target.data_ptr(), pred.data_ptr(),
+               dist[0].data_ptr() if band else None, dist[1].data_ptr() if band else None, out.data_ptr())
+    return out[0] if pred.dim() == 2 and out.dim() == 2 else out
+
+
+FILTER_DEFAULTS = dict(refine=0, refine_radius=3, refine_sigma_space=2.0, refine_sigma_colour=32.0, morph=False, min_area=0,
+                       connectivity=8, fill="neighbour", ignore_band=0, ignore_label=255)
+
+
+def check_filters(what="filters", **keywords):
+    """The keywords of ``apply_filters`` checked with the ``check_*`` functions above, without a tensor in sight -> the complete
+    keyword dict, defaults filled in (``fill`` as given, not as the C entry's number).  ValueError on a bad value and on a name that
+    is no keyword of ``apply_filters``."""
+    unknown = sorted(set(keywords) - set(FILTER_DEFAULTS))
+    if unknown:
+        raise ValueError("%s: %s is no keyword of apply_filters (%s)" % (what, ", ".join(map(repr, unknown)), ", ".join(FILTER_DEFAULTS)))
+    kw = dict(FILTER_DEFAULTS, **keywords)
+    if not isinstance(kw["morph"], bool):
+        raise ValueError("%s: morph must be True or False, got %r" % (what, kw["morph"]))
+    check_fill(kw["fill"], what + ": fill")
+    return dict(kw, refine=check_refine_iterations(kw["refine"], what + ": refine"),
+                refine_radius=check_refine_radius(kw["refine_radius"], what + ": refine_radius"),
+                refine_sigma_space=check_refine_sigma(kw["refine_sigma_space"], what + ": refine_sigma_space"),
+                refine_sigma_colour=check_refine_sigma(kw["refine_sigma_colour"], what + ": refine_sigma_colour"),
+                min_area=check_min_area(kw["min_area"], what + ": min_area"),
+                connectivity=check_connectivity(kw["connectivity"], what + ": connectivity"),
+                ignore_band=check_band(kw["ignore_band"], what + ": ignore_band"),
+                ignore_label=check_label(kw["ignore_label"], what + ": ignore_label"))
+
+
+_refine, _ignore_band = refine, ignore_band         # apply_filters has keywords of these names
+
+
+def apply_filters(img, mask, classes, refine=0, refine_radius=3, refine_sigma_space=2.0, refine_sigma_colour=32.0, morph=False, min_area=0,
+                  connectivity=8, fill="neighbour", ignore_band=0, ignore_label=255):
+    """The mask clean-up chain of ``ImageGenerator`` (its ``mask_*`` keywords without the prefix) on any pair, in its order: ``refine``
+    passes of ``refine(img, mask, classes=classes)`` with the three ``refine_*`` parameters, then ``morph_mask`` if ``morph``, then
+    ``despeckle(min_area, connectivity, fill)`` if ``min_area > 1``, then ``ignore_band(ignore_band, ignore_label)`` if ``ignore_band >
+    0``.  img (H, W, C) or (n, H, W, C) and mask (H, W) or (n, H, W) as ``refine`` takes them; ``classes`` 2..8, the class count the
+    refinement votes among.  Every keyword is checked before any device work, whether its stage is on or not.  Returns a new tensor;
+    with everything off, ``mask`` itself.  ``img`` is only looked at when ``refine > 0``."""
+    kw = check_filters(refine=refine, refine_radius=refine_radius, refine_sigma_space=refine_sigma_space, refine_sigma_colour=refine_sigma_colour,
+                       morph=morph, min_area=min_area, connectivity=connectivity, fill=fill, ignore_band=ignore_band, ignore_label=ignore_label)
+    classes = check_refine_classes(classes)
+    _check(mask, "mask")
+    if kw["refine"]:
+        mask = _refine(img, mask, kw["refine"], kw["refine_radius"], classes, sigma_space=kw["refine_sigma_space"],
+                       sigma_colour=kw["refine_sigma_colour"])
+    if kw["morph"]:
+        mask = morph_mask(mask)
+    if kw["min_area"] > 1:
+        mask = despeckle(mask, kw["min_area"], kw["connectivity"], kw["fill"])
+    if kw["ignore_band"]:
+        mask = _ignore_band(mask, kw["ignore_band"], kw["ignore_label"])
+    return mask

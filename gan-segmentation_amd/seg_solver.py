@@ -210,6 +210,57 @@ class SegSolver:
         result.append(("total-loss", total_loss / total_cnt if total_cnt else 0.0))
         return result
 
+    def evaluate_masks(self, input_dir, chains, band=2):
+        """The decoder's mask, passed through each filter chain of ``chains``, held against the annotations of ``input_dir`` (the
+        samples ``evaluate`` reads).  ``chains``: name -> keyword dict of ``mask_ops.apply_filters`` (``{}`` is the raw mask); ``band``:
+        0..32 px, the radius of the boundary band of ``mask_ops.compare``.  For every annotated sample the decoder's argmax mask stays
+        on the device, the stored image and the annotation (-1 written as 255) are uploaded, and every chain's result is compared
+        with the annotation (``compare(filtered, target, band)``) and with the raw mask (``compare(filtered, raw)``) there.  Returns
+        ``{name: [(metric, value), ...]}``: the five of ``metrics.MaskAgreement`` and ``changed``, the share of pixels the chain
+        altered.  Chain keywords are checked before any sample is read (ValueError)."""
+        from . import annotation_io, mask_ops
+        from .metrics import MaskAgreement
+        if not isinstance(chains, dict) or not chains:
+            raise ValueError("chains must be a non-empty dict: name -> keyword dict of mask_ops.apply_filters, got %r" % (chains,))
+        checked = {}
+        for name, kw in chains.items():
+            if not isinstance(kw, dict) or not all(isinstance(k, str) for k in kw):
+                raise ValueError("chain %r must be a dict of apply_filters keywords, got %r" % (name, kw))
+            checked[name] = mask_ops.check_filters("chain %r" % (name,), **kw)
+        band = mask_ops.check_band(band, "band")
+        if not self.is_trained:
+            raise RuntimeError("train Decoder first! (no checkpoint loaded)")
+        names = sorted(f for f in os.listdir(input_dir) if f.endswith(".pickle") and "feat" in f)
+        if not names:
+            raise ValueError("number of eval samples should be > 0")
+        nclass = self.cfg["num_classes"]
+        agreement = {name: MaskAgreement(nclass, skip_bg=True) for name in checked}
+        changed = {name: np.zeros((mask_ops.COMPARE_SLOTS, mask_ops.COMPARE_SLOTS), np.int64) for name in checked}
+        for fname in names:
+            image_id = int(os.path.splitext(fname)[0].split("_")[-1])
+            label, img, feats = annotation_io.load_sample(input_dir, image_id)
+            if label is None:
+                raise ValueError("no mask for %s" % fname)
+            _logits, raw = self.net(*feats, want_mask=True)
+            dev = raw.device
+            with torch.cuda.device(dev):
+                image = torch.from_numpy(np.array(img, np.uint8)).to(dev).reshape((1,) + img.shape)      # a copy: PIL's array is read-only
+                target = torch.from_numpy(np.where(label < 0, 255, label).astype(np.uint8)).to(dev).reshape(raw.shape)
+                rows = torch.empty((2 * len(checked), mask_ops.COMPARE_ROW), dtype=torch.int64, device=dev)
+                for i, kw in enumerate(checked.values()):
+                    filtered = mask_ops.apply_filters(image, raw, nclass, **kw)
+                    mask_ops.compare(filtered, target, band, out=rows[2 * i:2 * i + 1])
+                    mask_ops.compare(filtered, raw, out=rows[2 * i + 1:2 * i + 2])
+                host = rows.cpu().numpy()
+            for i, name in enumerate(checked):
+                agreement[name].update_rows(host[2 * i])
+                changed[name] += host[2 * i + 1, :mask_ops.COMPARE_SLOTS ** 2].reshape(changed[name].shape)
+        result = {}
+        for name in checked:
+            total = int(changed[name].sum())
+            result[name] = agreement[name].get_name_value() + [("changed", (total - int(np.trace(changed[name]))) / total)]
+        return result
+
     def _write_eval_sample(self, output_dir, image_id, img, feats, mask, conf, nclass):
         from PIL import Image
         from .metrics import SegmentationMetric
