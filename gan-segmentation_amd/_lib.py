@@ -146,6 +146,10 @@ UNIT_SIGNATURES = {
     "csrc/gsa_compare.h": {
         "gsa_mask_compare": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     },
+    "csrc/gsa_loss.h": {
+        "gsa_loss_workspace_bytes": (_i64, [_i32, _i32]),
+        "gsa_loss_softmax": (_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    },
 }
 
 

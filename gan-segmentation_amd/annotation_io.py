@@ -42,12 +42,17 @@ def preprocess_mask(mask_u8):
     return out
 
 
+def load_mask(db_dir, image_id):
+    """-> the labels of mask_%06d.png (int32: -1, 0, 1), or None where there is no such file."""
+    from PIL import Image
+    mpath = os.path.join(db_dir, "mask_%06d.png" % image_id)
+    return preprocess_mask(np.asarray(Image.open(mpath).convert("L"))) if os.path.exists(mpath) else None
+
+
 def load_sample(db_dir, image_id):
     """-> (mask int32 or None, img RGB u8, [features])  (reference seg_datasets.py:60-83)."""
     from PIL import Image
     img = np.asarray(Image.open(os.path.join(db_dir, "img_%06d.jpg" % image_id)).convert("RGB"))
     with open(os.path.join(db_dir, "feat_%06d.pickle" % image_id), "rb") as fp:
         feats = pickle.load(fp)
-    mpath = os.path.join(db_dir, "mask_%06d.png" % image_id)
-    mask = preprocess_mask(np.asarray(Image.open(mpath).convert("L"))) if os.path.exists(mpath) else None
-    return mask, img, feats
+    return load_mask(db_dir, image_id), img, feats

@@ -29,6 +29,11 @@ them, at quality 95), and they are not withheld by the device check that withhol
 one more line per chain: accuracy, mean-iou, band-accuracy, boundary-iou, abstained and changed of the decoder's mask passed through
 that chain, against the annotations under BASE_DIR/eval (``SegSolver.evaluate_masks``); the additive key ``EVAL_BAND`` (0..32 px,
 default 2) is the radius of the boundary band the two boundary figures are taken in.
+`train` takes the additive key ``TRAIN_LOSS`` (a mapping with keys among ``gamma``: 0 or 1..8, the focal exponent; ``normalise``:
+"mean", "valid" or "focal"; ``class_weights``: a list of one number per class, or "median" / "inverse", computed from the annotation
+masks under BASE_DIR/data; ``boundary``: a mapping with ``weight``, ``sigma`` and ``radius``, 1..32 px; absent by default: the
+reference's loss and nothing else) and trains the decoder with the loss of ``loss_ops`` (csrc/gsa_loss.h), the epoch lines then
+carrying the mean T/B as well.
 With torchrun (one process per GPU) the sample indices are sharded across ranks and every rank
 writes its own files -- no collective is needed when the sink is the filesystem.
 """
@@ -187,10 +192,22 @@ def _solver(cfg, keep_weights=False):
                      gpu_ids=gpu_ids, keep_weights=keep_weights, precision=cfg.get("PRECISION", "fp32"))
 
 
+def check_train_loss(v):
+    """The TRAIN_LOSS key: None (absent: the reference's loss), or a mapping with keys among gamma (0 or 1..8), normalise ("mean",
+    "valid" or "focal"), class_weights (a list of numbers, "median" or "inverse") and boundary (a mapping with weight, sigma and
+    radius) -> None or a ``loss_ops.LossSpec``.  ValueError otherwise, the message naming the key."""
+    from . import loss_ops
+    if v is None:
+        return None
+    return loss_ops.LossSpec.from_mapping(v, "TRAIN_LOSS")
+
+
 def train(cfg, epochs=None):
-    """The `train` action (reference main.py:54-60): fit the decoder on BASE_DIR/data, save the checkpoint."""
+    """The `train` action (reference main.py:54-60): fit the decoder on BASE_DIR/data, save the checkpoint.  With the additive key
+    ``TRAIN_LOSS`` the loss of ``loss_ops`` replaces the reference's (``SegSolver.fit(loss=...)``)."""
+    loss = check_train_loss(cfg.get("TRAIN_LOSS"))      # additive key, checked before any model is loaded
     solver = _solver(cfg, keep_weights=False)
-    history = solver.fit(epochs=epochs, log=print)
+    history = solver.fit(epochs=epochs, log=print, loss=loss)
     print("final loss: %.6f" % history[-1])
     return 0
 

@@ -135,16 +135,7 @@ def summarise(index, rows, H, W, C, num_classes=None):
         num_classes = 1 + max([s for s in range(SLOTS - 1) if pixels[s] > 0], default=0)
     num_classes = int(num_classes)
     frequency = [p / total for p in pixels]
-    present = [s for s in range(min(num_classes, SLOTS - 1)) if pixels[s] > 0]
-    inverse, median_f = [None] * SLOTS, [None] * SLOTS
-    if present:
-        raw = {s: 1.0 / frequency[s] for s in present}
-        scale = len(present) / sum(raw.values())
-        among = {s: pixels[s] / (presence[s] * plane) for s in present}
-        med = statistics.median(among.values())
-        for s in present:
-            inverse[s] = raw[s] * scale
-            median_f[s] = med / among[s]
+    inverse, median_f = frequency_weights(pixels, presence, plane, total, min(num_classes, SLOTS - 1))
     mean, std = [], []
     for c in range(C):
         mu = sum(r[f_csum + 4 * s + c] for r in table for s in range(SLOTS)) / total
@@ -163,6 +154,25 @@ def summarise(index, rows, H, W, C, num_classes=None):
         "empty_masks": sorted(i for i, v in zip(index, fg) if v == 0),
         "mean_edges": sum(r[f_eh] + r[f_ev] for r in table) / m,
     }
+
+
+def frequency_weights(pixels, presence, plane, total, classes):
+    """The two class-weight vectors "for the loss" from per-class counts: ``pixels[s]`` pixels of class s among ``total`` pixels (ignored
+    ones included) in samples of ``plane`` pixels, ``presence[s]`` samples that hold the class; the classes are 0 .. ``classes`` - 1.
+    -> (inverse, median), lists as long as ``pixels``, as ``summarise`` documents them: (1 / frequency[s]) scaled so that the weights of
+    the present classes have mean 1, and median(f) / f[s] with f[s] = pixels[s] / (presence[s] * plane).  None for a class without a
+    pixel and for every entry from ``classes`` up.  What ``summarise`` reports and ``loss_ops.class_weights_from_masks`` computes."""
+    inverse, median_f = [None] * len(pixels), [None] * len(pixels)
+    present = [s for s in range(classes) if pixels[s] > 0]
+    if present:
+        raw = {s: 1.0 / (pixels[s] / total) for s in present}
+        scale = len(present) / sum(raw.values())
+        among = {s: pixels[s] / (presence[s] * plane) for s in present}
+        med = statistics.median(among.values())
+        for s in present:
+            inverse[s] = raw[s] * scale
+            median_f[s] = med / among[s]
+    return inverse, median_f
 
 
 # ---- shard files -----------------------------------------------------------------------------------------------------------

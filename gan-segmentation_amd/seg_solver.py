@@ -93,24 +93,44 @@ class SegSolver:
         return mask.cpu().numpy().astype(np.float32)
 
     # -- training ---------------------------------------------------------
-    def fit(self, epoch_end_callback=None, epochs=None, seed=None, log=None):
+    def fit(self, epoch_end_callback=None, epochs=None, seed=None, log=None, loss=None):
         """Train the decoder on the annotated samples of ``path_to_data`` (``feat_*.pickle`` + ``mask_*.png``) as
         reference ``fit`` (:351-465): batch size 1, ``train_epochs`` epochs (24) of shuffled samples, Adam(1e-4),
         weighted softmax-CE, then ``save()``.  Every operator runs on the MI355X (``trainer.DecoderTrainer``).
         ``keep_weights=False`` starts from a fresh Xavier initialisation as the reference does.  Returns the mean
-        loss of each epoch."""
+        loss of each epoch.
+        ``loss``: None -- the reference's loss -- or a ``loss_ops.LossSpec`` (or a mapping of its keywords: gamma, normalise,
+        class_weights, boundary; ValueError on anything else, before a sample is read).  ``class_weights`` "median" or "inverse" are
+        computed on the host from the annotation masks of ``path_to_data`` (``loss_ops.class_weights_from_masks``; a class that no
+        mask holds gets weight 1: no pixel uses it).  With a spec the log line also carries the epoch's mean T/B, valid pixels over
+        focal mass (the reference's ``_k_sum``)."""
         import random
-        from . import annotation_io
+        from . import annotation_io, loss_ops
         from .trainer import DecoderTrainer
+        spec = loss_ops.check_spec(loss, "loss")
+        if spec is not None and not spec.needs_masks and spec.class_weights is not None:
+            loss_ops.check_class_weights(spec.class_weights, "loss: class_weights", num_classes=self.cfg["num_classes"], schemes=False)
         names = sorted(f for f in os.listdir(self.path_to_data) if f.endswith(".pickle") and "feat" in f)
         if not names:
             raise ValueError("number of training samples should be > 0")          # reference :139-141
+        if spec is not None and spec.needs_masks:
+            masks = []
+            for fname in names:
+                image_id = int(os.path.splitext(fname)[0].split("_")[-1])
+                mask = annotation_io.load_mask(self.path_to_data, image_id)
+                if mask is None:
+                    raise ValueError("no mask for %s" % fname)
+                masks.append(mask)
+            weights = loss_ops.class_weights_from_masks(masks, self.cfg["num_classes"], spec.class_weights)
+            spec = spec.with_class_weights([1.0 if w is None else w for w in weights])
+            if log is not None:
+                log("loss class weights: %s" % ", ".join("%.6f" % w for w in spec.class_weights))
         seed = 1 if seed is None else seed                                          # reference cfg['seed'] = 1
         if self.keep_weights and getattr(self.net, "_tensors", None) is not None:
             start = self.net._tensors
         else:
             start = _weights.initial_decoder_params(self.cfg, seed)
-        tr = DecoderTrainer(self.cfg, start, device=self.ctx[0], lr=1e-4, wd=0.0, seed=seed)     # reference cfg: adam, base_lr 1e-4, wd 0
+        tr = DecoderTrainer(self.cfg, start, device=self.ctx[0], lr=1e-4, wd=0.0, seed=seed, loss=spec)     # reference cfg: adam, base_lr 1e-4, wd 0
         epochs = 24 if epochs is None else epochs                                                # reference cfg['train_epochs']
         rng = random.Random(seed)
         history = []
@@ -125,15 +145,22 @@ class SegSolver:
             rng.shuffle(order)           # the same permutation on every rank (same seed) ...
             if world > 1:                           # ... of which rank r takes every world-th sample: the trainer
                 order = order[:len(order) - len(order) % world][rank::world]   # all-reduces the gradients, so a step sees `world` samples
-            total = 0.0
+            total, ratios = 0.0, []
             for fname in order:
                 image_id = int(os.path.splitext(fname)[0].split("_")[-1])
                 mask, _img, feats = annotation_io.load_sample(self.path_to_data, image_id)
                 if mask is None:
                     raise ValueError("no mask for %s" % fname)
                 total += tr.step(feats, mask[None])
+                if spec is not None:
+                    ratios.append(tr.last_sums)     # on the device: read once an epoch
             history.append(total / len(order))
-            if log is not None:
+            if log is not None and spec is not None:
+                sums = torch.cat(ratios).cpu().numpy()
+                live = sums[:, loss_ops.SUM_B] > 0
+                t_over_b = float(np.mean(sums[live, loss_ops.SUM_T] / sums[live, loss_ops.SUM_B])) if live.any() else 0.0
+                log("Epoch[%d] Train-total-loss=%f T/B=%f" % (epoch + 1, history[-1], t_over_b))
+            elif log is not None:
                 log("Epoch[%d] Train-total-loss=%f" % (epoch + 1, history[-1]))
             if epoch_end_callback is not None:
                 epoch_end_callback()

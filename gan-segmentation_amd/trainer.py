@@ -16,6 +16,8 @@ import math
 import numpy as np
 import torch
 
+from . import loss_ops as _loss_ops
+from . import mask_ops as _mask_ops
 from . import train_ops as ops
 from . import weights as _weights
 from ._runtime import require_gpu
@@ -23,7 +25,9 @@ from ._runtime import require_gpu
 
 class DecoderTrainer:
     def __init__(self, cfg, params, device=0, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, seed=1,
-                 dropout_keep=0.5, sync_bn=None, all_reduce=None, world=None):
+                 dropout_keep=0.5, sync_bn=None, all_reduce=None, world=None, loss=None):
+        """``loss``: None -- the reference's loss, ``train_ops.softmax_ce`` -- or a ``loss_ops.LossSpec`` (or a mapping of its keywords)
+        with numeric class weights: the step then calls ``loss_ops.softmax_loss`` and keeps its sums in ``last_sums``."""
         require_gpu()
         if not cfg["use_bn"]:
             raise NotImplementedError("training supports the reference's configuration: use_bn=True")
@@ -42,6 +46,20 @@ class DecoderTrainer:
         self.sync_bn = bool(cfg.get("use_sync_bn", False)) if sync_bn is None else bool(sync_bn)
         self._all_reduce = all_reduce if all_reduce is not None else self._dist_all_reduce
         self._world_override = world    # with a caller-supplied all_reduce: the number of ranks it sums over
+        # the loss of loss_ops: class weights and the boundary table go to the device once
+        self.loss = _loss_ops.check_spec(loss, "loss")
+        self.last_sums = None       # (n, 4) float64 [W, B, S, T] of the last step with a spec; T / B is the reference's _k_sum
+        self._loss_cw = self._loss_table = self._loss_workspace = None
+        if self.loss is not None:
+            if self.loss.needs_masks:
+                raise ValueError("loss: class_weights %r must be numbers here (SegSolver.fit computes them from its masks)"
+                                 % (self.loss.class_weights,))
+            if self.loss.class_weights is not None:
+                weights = _loss_ops.check_class_weights(self.loss.class_weights, "loss: class_weights", num_classes=int(self.F[-1]),
+                                                        schemes=False)
+                self._loss_cw = torch.tensor(weights, dtype=torch.float32).to(self.dev)
+            if self.loss.boundary is not None:
+                self._loss_table = torch.from_numpy(self.loss.table()).to(self.dev)
         shapes = _weights.decoder_param_shapes(cfg)
         self.p, self.g, self.m, self.v = {}, {}, {}, {}
         for name, shape in shapes.items():
@@ -134,7 +152,10 @@ class DecoderTrainer:
                 logits, _ = ops.conv(src0, src1, p[fn + ".weight"], p[fn + ".bias"])
             saved[i] = rec
 
-        loss, dlogits = ops.softmax_ce(logits, lab)
+        if self.loss is None:
+            loss, dlogits = ops.softmax_ce(logits, lab)
+        else:
+            loss, dlogits = self._spec_loss(logits, lab)
 
         # ---- backward
         dprev = None        # gradient w.r.t. the output of main block i-1 (`prev` of level i)
@@ -181,6 +202,20 @@ class DecoderTrainer:
         for name in g:
             ops.adam(p[name], g[name], self.m[name], self.v[name], lr_t, self.b1, self.b2, self.eps, rescale=1.0 / (n * world), wd=self.wd)
         return float(loss.cpu().numpy().mean())
+
+    def _spec_loss(self, logits, lab):
+        """The loss of ``self.loss`` in place of softmax_ce.  With a boundary the per-pixel weight is read from the squared distance
+        to the nearest pixel of another label, the ignore label being a value like any other (the int8 plane read as uint8: -1 is
+        255), so the rim of an unlabelled region counts as a boundary; its unlabelled side has weight 0 anyway."""
+        dist2 = None
+        if self._loss_table is not None:
+            dist2 = _mask_ops.boundary_distance(lab.view(torch.uint8), self.loss.boundary["radius"])
+        need = _loss_ops.workspace_bytes(lab.shape[0], lab[0].numel())
+        if self._loss_workspace is None or self._loss_workspace.numel() < need:
+            self._loss_workspace = torch.empty(need, device=self.dev, dtype=torch.uint8)
+        loss, self.last_sums, dlogits = _loss_ops.softmax_loss(logits, lab, self.loss, class_weights=self._loss_cw, dist2=dist2,
+                                                               table=self._loss_table, workspace=self._loss_workspace)
+        return loss, dlogits
 
     def _eye(self, C):
         e = self._eyes.get(C)
