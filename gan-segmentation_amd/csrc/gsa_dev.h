@@ -150,6 +150,46 @@ __device__ __forceinline__ void mfma_settle(f32x4 (&a)[16]) {
                    "+v"(a[9]), "+v"(a[10]), "+v"(a[11]), "+v"(a[12]), "+v"(a[13]), "+v"(a[14]), "+v"(a[15]));
 }
 
+// loads_landed(registers [, pin]): the global loads that fill `registers` have completed behind this statement.  Nothing is emitted
+// for it: the registers are in/out operands of an EMPTY asm, so the compiler's own wait insertion places the s_waitcnt that the first
+// real use would otherwise get -- here, where the item loops want it, instead of at that use.  The vector-memory counter counts loads,
+// LDS-DMA pieces, stores and atomics alike.  A prefetched register set whose first use is the NEXT iteration's staging gets its wait at
+// the loop head, behind the epilogue's stores and atomics, and with a count the compiler takes from the loop-entry state (nothing but the
+// loads in flight): vmcnt(1), vmcnt(0) -- the item waits until the previous item's OUTPUT is acknowledged before it may stage a tile that
+// has long arrived (profiles/r07_isa_waits.txt).  Retired at the end of the MFMA phase, before any store of the epilogue, and once in
+// front of the loop, the same registers cost the loop head no wait at all and the stores stay in flight across the closing barrier.
+// `pin` is an accumulator the last MFMA of the phase writes: the statement is ordered by its operands only, and the accumulator keeps it
+// behind the multiply (without it the scheduler may put the wait directly behind the loads).
+#define GSA_LANDED_1(x) "+v"(x)
+#define GSA_LANDED_2(r) GSA_LANDED_1((r)[0]), GSA_LANDED_1((r)[1])
+#define GSA_LANDED_3(r) GSA_LANDED_2(r), GSA_LANDED_1((r)[2])
+#define GSA_LANDED_6(r) GSA_LANDED_3(r), GSA_LANDED_1((r)[3]), GSA_LANDED_1((r)[4]), GSA_LANDED_1((r)[5])
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[2]) { asm("" : GSA_LANDED_2(r)); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[3]) { asm("" : GSA_LANDED_3(r)); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[6]) { asm("" : GSA_LANDED_6(r)); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[1][2]) { asm("" : GSA_LANDED_2(r[0])); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[2][2]) { asm("" : GSA_LANDED_2(r[0]), GSA_LANDED_2(r[1])); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[2], f32x4& pin) { asm("" : GSA_LANDED_2(r), "+v"(pin)); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[3], f32x4& pin) { asm("" : GSA_LANDED_3(r), "+v"(pin)); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[6], f32x4& pin) { asm("" : GSA_LANDED_6(r), "+v"(pin)); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[1][2], f32x4& pin) { asm("" : GSA_LANDED_2(r[0]), "+v"(pin)); }
+__device__ __forceinline__ void loads_landed(f32x4 (&r)[2][2], f32x4& pin) { asm("" : GSA_LANDED_2(r[0]), GSA_LANDED_2(r[1]), "+v"(pin)); }
+// vmem_drained(pin): the same place for the kernels that also stream weights by LDS-DMA -- everything the wave has issued (the next
+// item's DMA pieces, the loads of the item after it) has arrived, behind the MFMA phase and before the epilogue's first store.  An
+// explicit s_waitcnt vmcnt(0) (expcnt and lgkmcnt left alone: 0x0F70) through the builtin, which the compiler's wait insertion reads:
+// it then knows that no LDS-DMA piece is pending at the closing barrier and emits a bare s_barrier.  With a piece pending in ITS books
+// -- an inline-asm counted wait tells it nothing -- the release fence of __syncthreads() gets vmcnt(0) lgkmcnt(0), which waits for the
+// tile-end stores and the statistics atomics as well, and the first use of a loaded register beside a pending piece gets vmcnt(0)
+// instead of a count, which waits for pieces issued a few instructions earlier.
+__device__ __forceinline__ void vmem_drained(f32x4& pin) {
+    asm volatile("" : "+v"(pin));      // volatile: keeps its order with the wait; the operand keeps both behind the last MFMA
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+}
+#undef GSA_LANDED_6
+#undef GSA_LANDED_3
+#undef GSA_LANDED_2
+#undef GSA_LANDED_1
+
 // more packed fp32 operations (IEEE, the same bits as the scalar forms)
 __device__ __forceinline__ f32x2 pk_mul2(f32x2 a, f32x2 b) { f32x2 r; asm("v_pk_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // a * b.x and a * b.y (both halves of the product take ONE half of b: op_sel picks the dword of the 64-bit source)

@@ -7,8 +7,8 @@
 //   * staging by 16-byte chunks on ALL 256 threads of a half (400 chunks = 2 rounds) instead of whole pixels on 100 of them; the AdaIN
 //     coefficients of the sample sit in an LDS table as (A x 16 | B x 16) per block (two LDS reads and two packed fma per chunk instead of
 //     16 table reads + 16 fma per pixel); global addresses are a wave-uniform base plus per-thread constants; border flags in one word;
-//   * streamed weights go to the LDS ring by LDS-DMA (no staging registers, no LDS stores), waited for with a counted vmcnt before the
-//     iteration's closing barrier;
+//   * streamed weights go to the LDS ring by LDS-DMA (no staging registers, no LDS stores), waited for behind the iteration's MFMA phase
+//     together with the prefetched activations;
 //   * the chains of a tile's first block start from the inline constant 0 (no accumulator clearing); the epilogue is packed.
 #include "gsa_kernels.h"
 #include "gsa_dev.h"
@@ -46,7 +46,6 @@ __global__ __launch_bounds__(512, 2) void subpixel_lean(ConvParams p) {
     static_assert(!WST || KB == 1, "streamed weights: one channel block per item");
     static_assert(!CNT || !WST, "counter hand-over: the resident-panel form");
     constexpr int NBUF = CNT ? 3 : 2;
-    constexpr int NSTORES = 4 * NT + (SC ? NT : 0);      // global stores of one epilogue per wave
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int nblk0 = p.C0 >> 4, nblk = (p.C0 + p.C1) >> 4, nitem = nblk / KB;
     const int wblk = WST ? 2 : nblk;
@@ -296,6 +295,7 @@ __global__ __launch_bounds__(512, 2) void subpixel_lean(ConvParams p) {
         if (AFF && tr.n != n_tab) { fill_coefficients(tr.n); n_tab = tr.n; }
         load_item(tr, er, cir);
     }
+    loads_landed(ra);                                                 // no path reaches the loop head with loads in flight
     __syncthreads();
     unsigned long long k0 = 0, k1 = 0, k2 = 0, k3 = 0, k4 = 0, k5 = 0, sw = 0, sl = 0, sm = 0, se = 0, sb = 0;      // diagnostic build only (make stamp)
     (void)k0; (void)k1; (void)k2; (void)k3; (void)k4; (void)k5; (void)sw; (void)sl; (void)sm; (void)se; (void)sb;
@@ -353,13 +353,11 @@ __global__ __launch_bounds__(512, 2) void subpixel_lean(ConvParams p) {
     for (int it = 0; it < iters; ++it) {
         TICK(k0);
         if (WST && it + 1 < iters) dma_block((it + 1) % nblk, (it + 1) & 1);      // the slot iteration it - 1 read: every wave is past its closing barrier
-        bool stored = false, loaded = false;
         if (it < total_items) {
             if (it + 1 < total_items) write_item(tr, er, cir, (it + 1) & 1);
             TICK(k1);
             STile t2 = tr; int e2c = er, ci2 = cir;
             if (it + 2 < total_items) {
-                loaded = true;
                 next_item(t2, e2c, ci2);
                 if (AFF && t2.n != n_tab) { fill_coefficients(t2.n); n_tab = t2.n; }
                 load_item(t2, e2c, ci2);
@@ -372,20 +370,18 @@ __global__ __launch_bounds__(512, 2) void subpixel_lean(ConvParams p) {
                 if (kb == 0 && cic == 0) mfma_block(std::true_type{}, a_buf + kb * SIMG, wslot);
                 else mfma_block(std::false_type{}, a_buf + kb * SIMG, wslot);
             }
+            // item it + 2, staged by the next iteration, is waited for here: the multiply has covered its loads and no store of this tile
+            // is in flight yet -- at the loop head the wait would be for a tile-ending iteration's stores as well (loads_landed, gsa_dev.h).
+            // Streamed weights: the ring slot's DMA pieces with it (vmem_drained): no counted wait at the barrier, which is then a bare one
+            if constexpr (WST) vmem_drained(acc[8][NT - 1]);
+            else loads_landed(ra, acc[8][NT - 1]);
             TICK(k3);
-            if (cic == nitem - 1) { epilogue(tc); stored = true; }
+            if (cic == nitem - 1) epilogue(tc);
             TICK(k4);
             tc = tr; ec = er; cic = cir; tr = t2; er = e2c; cir = ci2;
         }
-        if (WST) {
-            // this wave's DMA pieces are older than the loads of item it + 2 and the epilogue's stores (in-order completion): with at most that
-            // many operations outstanding the pieces are in LDS, the younger operations stay in flight
-            // (an iteration that issued fewer of them waits for correspondingly more)
-            if (stored && loaded) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * KB + NSTORES) : "memory");
-            else if (loaded) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * KB) : "memory");
-            else if (stored) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NSTORES) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        // streamed weights, a half that has run out of items (it still issues its share of the DMA pieces): nothing else is in flight
+        if (WST && it >= total_items) __builtin_amdgcn_s_waitcnt(0x0F70);
         __syncthreads();
         TICK(k5);
         if (it < total_items) { TSUM(sw, k0, k1); TSUM(sl, k1, k2); TSUM(sm, k2, k3); TSUM(se, k3, k4); TSUM(sb, k4, k5); }

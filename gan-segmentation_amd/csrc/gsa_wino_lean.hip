@@ -46,9 +46,12 @@ struct Tile { int n, y0, x0; };
 // buffer is refilled with the next item while the MFMAs run out of registers: 37 KB of LDS per workgroup, so THREE workgroups per CU when
 // the kernel also fits 168 registers (more waves instead of bigger items).
 // PF = register sets of the activation prefetch: 1 = item it+2 is loaded while item it is multiplied (one item time between a load and its
-// use); 2 = item it+3 (two item times).  The 16 -> 16 layers at 1024^2 read and write 1.07 GB per launch -- they sit on the HBM roof, and
-// the stamps of the PF = 1 form (profiles/r05_stamps_lean.txt: write phase ~2100 of ~8100 cycles per item for six chunk stores) show the
-// staging writes WAITING for loads issued one item earlier: under a saturated memory system one item time (~3.5 us) does not cover a load.
+// use); 2 = item it+3 (two item times).  The 16 -> 16 layers at 1024^2 read and write 1.07 GB per launch -- they sit on the HBM roof.  The
+// stamps of the PF = 1 form (profiles/r05_stamps_lean.txt: write phase ~2100 of ~8100 cycles per item for six chunk stores) were read as
+// the staging writes waiting for loads issued one item earlier; the emitted code (profiles/r07_isa_waits.txt) shows what the wait in
+// front of them was: vmcnt(1), vmcnt(0) behind the epilogue's four stores -- a wait for the previous item's OUTPUT.  Round 7 retires the
+// prefetched set behind the MFMA phase instead (loads_landed, gsa_dev.h); measured, d.main_7.b gained 4 %, the other two layers nothing,
+// with one prefetch set or two.
 // RGB (16 -> 16, decoder epilogue, AdaIN source): toRGB + _transform_gan_back (reference networks_stylegan.py:118-126, image_generator.py:76-84) of
 // the SAME tile out of the staged LDS image -- the decoder's last cvt conv and toRGB both read the generator's last feature with the same AdaIN
 // coefficients, and the staged value fmaf(x, A, B) is exactly what toRGB's chain starts from; thread = pixel of the 16x16 tile, the canonical
@@ -360,6 +363,7 @@ __global__ __launch_bounds__(256 * GW, GW == 1 ? (DB ? 2 : 3) : 1) void conv3x3_
         Tile t2 = tc, t3; int e2c = ec, cb2 = 0, e3c, cb3;
         if (items > 1) { next_item(tr, er, cbr); load_item(S1{}, tr, er, cbr); t2 = tr; e2c = er; cb2 = cbr; }
         if (items > 2) { next_item(t2, e2c, cb2); load_item(S0{}, t2, e2c, cb2); }
+        loads_landed(ra[PF - 1]);               // item 1, staged by the first iteration (item 2 stays in flight)
         __syncthreads();
         auto body = [&](auto set_tag, int it) {      // set_tag: the register set of item it+1 (and of item it+3)
             const bool has_next = it + 1 < items;
@@ -372,6 +376,9 @@ __global__ __launch_bounds__(256 * GW, GW == 1 ? (DB ? 2 : 3) : 1) void conv3x3_
             TICK(k2);
             if (NB == 1 || cbc == 0) multiply(std::true_type{}, it & 1, 0);
             else multiply(std::false_type{}, it & 1, cbc);
+            // the OTHER set (item it+2, loaded an iteration ago, staged by the next iteration): waited for here, in front of the epilogue's
+            // stores, with the loads of item it+3 left in flight -- the next iteration's staging then waits for nothing (loads_landed, gsa_dev.h)
+            loads_landed(ra[PF - 1 - decltype(set_tag)::value], acc[15]);
             TICK(k3);
             if (cbc == NB - 1) {
                 epilogue(tc);
@@ -392,6 +399,7 @@ __global__ __launch_bounds__(256 * GW, GW == 1 ? (DB ? 2 : 3) : 1) void conv3x3_
         return;
     }
     if (items > 1) { next_item(tr, er, cbr); load_item(S0{}, tr, er, cbr); }
+    loads_landed(ra[0]);                        // no path reaches the loop head with loads in flight
     __syncthreads();
     if constexpr (DB) {
         for (int it = 0; it < items; ++it) {
@@ -405,6 +413,9 @@ __global__ __launch_bounds__(256 * GW, GW == 1 ? (DB ? 2 : 3) : 1) void conv3x3_
             TICK(k2);
             if (NB == 1 || cbc == 0) multiply(std::true_type{}, it & 1, 0);
             else multiply(std::false_type{}, it & 1, cbc);
+            // item it+2, staged by the next iteration: its wait belongs here, where the multiply has covered the loads and no store of
+            // this item is in flight yet -- at the loop head it would wait for the epilogue's stores as well (loads_landed, gsa_dev.h)
+            loads_landed(ra[0], acc[15]);
             TICK(k3);
             if constexpr (RGB) torgb(tc, it & 1);
             if (cbc == NB - 1) {
@@ -429,6 +440,7 @@ __global__ __launch_bounds__(256 * GW, GW == 1 ? (DB ? 2 : 3) : 1) void conv3x3_
             Tile t2 = tr; int e2c = er, cb2 = 0;
             if (it + 2 < items) { next_item(t2, e2c, cb2); load_item(S0{}, t2, e2c, cb2); }
             mfmas(std::true_type{}, 0);
+            loads_landed(ra[0], acc[15]);       // as in the double-buffered loop: in front of the epilogue's stores
             epilogue(tc);
             if (EPI == EPI_SYNTH && (!has_next || tr.n != tc.n)) flush_stats(tc.n);
             __syncthreads();                    // item it + 1 is complete in the buffer
@@ -463,8 +475,8 @@ __device__ __forceinline__ void antiphase_start(int cycles64, float* lds_word) {
 // One workgroup = 4 waves on 16x16 tiles x ONE 16-channel output group (blockIdx.y), an item = (tile, 16-channel block).  As conv3x3_wino<EPI, 1,
 // true, AFF, 1>: double-buffered image and weight block, activations prefetched two items ahead through registers, accumulators across the
 // blocks of a tile, direct statistics.  What is leaner: the item's 16 KB weight block goes to LDS by LDS-DMA (global_load_lds_dwordx4: four
-// 1 KB pieces per wave, issued one item ahead into the buffer the previous item has left, waited for with a counted vmcnt before the item's
-// closing barrier) -- no staging registers, no LDS stores, and room for the accumulators beside the prefetch; the sample's AdaIN coefficients sit in
+// 1 KB pieces per wave, issued one item ahead into the buffer the previous item has left, waited for behind the item's MFMA phase together
+// with the prefetched activations: vmem_drained, gsa_dev.h) -- no staging registers, no LDS stores, and room for the accumulators beside the prefetch; the sample's AdaIN coefficients sit in
 // a 4 KB LDS table as (A x 16 | B x 16) per block -- two LDS reads per item instead of four global loads of (mean, A, B, -) entries -- and are
 // applied with packed fma; wave-uniform global bases; border flags in one word; weights as the A operand, so the epilogue of the tile's last
 // block is the transposition-free packed one of conv3x3_wino_lean; the chains of a tile's first block start from the inline constant 0.
@@ -801,19 +813,11 @@ __device__ __forceinline__ void wino_stream_body(const ConvParams& p) {
     load_item(tc, ec, 0);
     write_item(tc, ec, 0, 0);
     tr = tc; er = ec;
-    // "at most NCH vector-memory operations outstanding": this thread's NCH activation loads of the item in flight are the youngest loads
-    auto wait_all_but_loads = [&]() {
-        static_assert(NCH == 6 || NCH == 3, "the counted wait is spelled per staging-round count");
-        if constexpr (NCH == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    };
     if (items > 1) {
         next_item(tr, er, cbr);
         load_item(tr, er, cbr);
-        wait_all_but_loads();      // the four DMA pieces are older than the NCH (six; PAIR: three) loads of the second item
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
+    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): the first panel's DMA pieces, and no path reaches the loop head with loads in flight
     __syncthreads();
     unsigned long long k0 = 0, k1 = 0, k2 = 0, k3 = 0, k4 = 0, k5 = 0, sw = 0, sl = 0, sm = 0, se = 0, sb = 0;      // diagnostic build only (make stamp)
     (void)k0; (void)k1; (void)k2; (void)k3; (void)k4; (void)k5; (void)sw; (void)sl; (void)sm; (void)se; (void)sb;
@@ -833,20 +837,19 @@ __device__ __forceinline__ void wino_stream_body(const ConvParams& p) {
         auto vm1 = [&]() { if (IL == 1 && it + 2 < items) load_item(t2, e2c, cb2); };
         if (cbc == 0) multiply(std::true_type{}, it & 1, vm0, vm1);
         else multiply(std::false_type{}, it & 1, vm0, vm1);
+        // This wave's DMA pieces of item it + 1 and its loads of item it + 2 have the multiply to arrive in; they are waited for HERE, in
+        // front of the epilogue -- not by a counted wait at the closing barrier.  That wait (vmcnt(NCH): "everything but the loads") was
+        // dead: the compiler, with DMA pieces pending in its books, gave the barrier's fence vmcnt(0) lgkmcnt(0), which drained the
+        // tile-end stores and the statistics atomics too, and gave the first staging store of the next iteration vmcnt(0) directly behind
+        // the four pieces that iteration had just issued (profiles/r07_isa_waits.txt).  Now the pieces have landed before any wave passes
+        // the barrier, the barrier is a bare s_barrier, and what stays in flight across it are the stores and the atomics.
+        vmem_drained(accs[NT - 1][15]);
         TICK(k3);
         if (cbc == nblk - 1) {
             epilogue(tc);
             if (EPI == EPI_SYNTH && (!has_next || tr.n != tc.n)) flush_stats(tc.n);
         }
         TICK(k4);
-        // this wave's DMA pieces have landed before anybody passes the barrier: they are older than the six loads of item it + 2 (in-order
-        // completion), so at most six outstanding operations means the pieces are in LDS and the younger loads stay in flight; an
-        // iteration that issued no such loads (the last two) waits for everything.  PAIR: the instruction order of an iteration is the
-        // same -- four DMA pieces, [two noise loads], the item's activation loads, [the epilogue's stores and atomics] -- with THREE
-        // activation loads per thread (1296 chunks over 512 threads), so the count is three: of 4 + x + 3 operations at most x are not
-        // loads, loads complete in order, hence 4 + x completions include the four pieces whichever x complete early
-        if (it + 2 < items) wait_all_but_loads();
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         TICK(k5);
         TSUM(sw, k0, k1); TSUM(sl, k1, k2); TSUM(sm, k2, k3); TSUM(se, k3, k4); TSUM(sb, k4, k5);
@@ -894,9 +897,9 @@ bool single_buffered() {
 }
 
 // GSA_WINO_LEAN_PF=1 | 2: register sets of the activation prefetch of the 16 -> 16 kernels (speed only, same bits).  Measured equal (same box,
-// FFHQ batch 8: d.cvt_8 0.228 / 0.232 ms, d.main_7.b 0.260 / 0.257, g.1024.conv_2 0.257 / 0.259 with one / two sets): the wait in front of
-// the staging writes is the memory system's throughput (1.1-1.2 GB of traffic in 0.23 ms), not the distance between a load and its use.
-// Default: one set (24 registers fewer).
+// FFHQ batch 8: d.cvt_8 0.228 / 0.232 ms, d.main_7.b 0.260 / 0.257, g.1024.conv_2 0.257 / 0.259 with one / two sets), and equal again in
+// round 7 with the loop head's wait for the previous item's stores gone (0.260-0.263 / 0.261-0.264, 0.240-0.250 / 0.243-0.252, 0.260-0.263 /
+// 0.265-0.267): not the distance between a load and its use.  Default: one set (24 registers fewer).
 int prefetch_sets() {
     static const int pf = env_int("GSA_WINO_LEAN_PF", 1);
     return pf == 2 ? 2 : 1;
