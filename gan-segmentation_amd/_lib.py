@@ -150,6 +150,9 @@ UNIT_SIGNATURES = {
         "gsa_loss_workspace_bytes": (_i64, [_i32, _i32]),
         "gsa_loss_softmax": (_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),
     },
+    "csrc/gsa_scores.h": {
+        "gsa_score_histogram": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    },
 }
 
 

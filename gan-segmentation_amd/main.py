@@ -28,7 +28,11 @@ them, at quality 95), and they are not withheld by the device check that withhol
 ``morph: true`` or ``ignore_band: 2``, empty for the raw mask; absent by default: the reference's one line and nothing else) and prints
 one more line per chain: accuracy, mean-iou, band-accuracy, boundary-iou, abstained and changed of the decoder's mask passed through
 that chain, against the annotations under BASE_DIR/eval (``SegSolver.evaluate_masks``); the additive key ``EVAL_BAND`` (0..32 px,
-default 2) is the radius of the boundary band the two boundary figures are taken in.
+default 2) is the radius of the boundary band the two boundary figures are taken in.  The additive key ``EVAL_SCORES: true`` (default
+false) prints one more line after those: mean-auc, mean-ap, the reference's 100*(1-mean-auc) and 100*(1-mean-ap), and per class the best
+margin threshold with its IoU, the IoU at margin 0 and the share of clamped pixels, read from the histograms of the decoder's logit
+margins (``SegSolver.evaluate_scores``, csrc/gsa_scores.h); the additive key ``EVAL_SCORE_SHIFT`` (0..8, default 5) gives them 2^shift bins
+per logit unit.
 `train` takes the additive key ``TRAIN_LOSS`` (a mapping with keys among ``gamma``: 0 or 1..8, the focal exponent; ``normalise``:
 "mean", "valid" or "focal"; ``class_weights``: a list of one number per class, or "median" / "inverse", computed from the annotation
 masks under BASE_DIR/data; ``boundary``: a mapping with ``weight``, ``sigma`` and ``radius``, 1..32 px; absent by default: the
@@ -235,12 +239,28 @@ def check_eval_band(v):
     return mask_ops.check_band(v, "EVAL_BAND")
 
 
+def check_eval_scores(v):
+    """The EVAL_SCORES key: a bool (ValueError otherwise)."""
+    if not isinstance(v, bool):
+        raise ValueError("EVAL_SCORES must be true or false, got %r" % (v,))
+    return v
+
+
+def check_eval_score_shift(v):
+    """The EVAL_SCORE_SHIFT key: 2^shift bins per logit unit in the score histograms, an int 0 .. 8 (ValueError otherwise)."""
+    from . import score_ops
+    return score_ops.check_shift(v, "EVAL_SCORE_SHIFT")
+
+
 def evaluate(cfg):
     """The `evaluate` action (reference main.py:61-73) over BASE_DIR/eval.  With the additive key ``EVAL_MASK_CHAINS`` one more line
-    per chain: the decoder's mask through that filter chain against the annotations (``SegSolver.evaluate_masks``)."""
+    per chain: the decoder's mask through that filter chain against the annotations (``SegSolver.evaluate_masks``).  With the
+    additive key ``EVAL_SCORES`` one more line: the figures of ``metrics.ScoreCurves`` (``SegSolver.evaluate_scores``)."""
     # additive keys, checked before any model is loaded
     chains = check_eval_mask_chains(cfg.get("EVAL_MASK_CHAINS"))
     band = check_eval_band(cfg.get("EVAL_BAND", 2))
+    scores = check_eval_scores(cfg.get("EVAL_SCORES", False))
+    score_shift = check_eval_score_shift(cfg.get("EVAL_SCORE_SHIFT", 5))
     solver = _solver(cfg)
     if not solver.is_trained:
         print("train Decoder first!")
@@ -251,6 +271,9 @@ def evaluate(cfg):
     if chains is not None:
         for chain, values in solver.evaluate_masks(eval_dir, chains, band=band).items():
             print("%s: %s" % (chain, ", ".join("%s: %.4f" % (name, value) for name, value in values)))
+    if scores:
+        curves = solver.evaluate_scores(eval_dir, shift=score_shift)
+        print("scores: %s" % ", ".join("%s: %.4f" % (name, value) for name, value in curves.get_name_value()))
     return 0
 
 

@@ -288,6 +288,37 @@ class SegSolver:
             result[name] = agreement[name].get_name_value() + [("changed", (total - int(np.trace(changed[name]))) / total)]
         return result
 
+    def evaluate_scores(self, input_dir, shift=5):
+        """How well the decoder's logits separate each class over the annotated samples of ``input_dir`` (the samples ``evaluate``
+        reads): for every sample a decoder forward, one ``score_ops.score_histogram`` of its logits against the annotation on the
+        device, and one copy of the (K, 2, 1024) row to the host.  ``shift``: 0..8, 2^shift bins per logit unit.  Returns the
+        ``metrics.ScoreCurves`` of all samples: ROC-AUC, average precision, the threshold sweep and the best margin threshold of
+        every class.  ``shift`` is checked before any sample is read (ValueError)."""
+        from . import annotation_io, score_ops
+        from .metrics import ScoreCurves
+        shift = score_ops.check_shift(shift)
+        if not isinstance(input_dir, (str, os.PathLike)):
+            raise ValueError("input_dir must be a path, got %r" % (input_dir,))
+        if not self.is_trained:
+            raise RuntimeError("train Decoder first! (no checkpoint loaded)")
+        names = sorted(f for f in os.listdir(input_dir) if f.endswith(".pickle") and "feat" in f)
+        if not names:
+            raise ValueError("number of eval samples should be > 0")
+        nclass = self.cfg["num_classes"]
+        curves = ScoreCurves(nclass, shift=shift, skip_bg=True)
+        for fname in names:
+            image_id = int(os.path.splitext(fname)[0].split("_")[-1])
+            label, _img, feats = annotation_io.load_sample(input_dir, image_id)
+            if label is None:
+                raise ValueError("no mask for %s" % fname)
+            logits, _mask = self.net(*feats, want_mask=True)
+            n, _k, H, W = logits.shape
+            dev = logits.device
+            with torch.cuda.device(dev):
+                lab = torch.as_tensor(np.asarray(label)).reshape(n, H, W).to(device=dev, dtype=torch.int8).contiguous()
+                curves.update_rows(score_ops.score_histogram(logits, lab, shift=shift).cpu().numpy())
+        return curves
+
     def _write_eval_sample(self, output_dir, image_id, img, feats, mask, conf, nclass):
         from PIL import Image
         from .metrics import SegmentationMetric
