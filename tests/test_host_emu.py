@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 from tests import test_gpu_augment as gpu_augment, test_gpu_boundary as gpu_boundary, test_gpu_photometric as gpu_photometric
+from tests.extent_cases import LONG_THIN, PHOTOMETRIC_THIN, thin_masks
 from tests.test_augment_host import random_pair, rule_augment
 from tests.test_boundary_host import class_blobs, has_both, rule_band, rule_boundary
 from tests.test_mask_morph_host import SEAM_SHAPES, SMALL_SHAPES, make, rule_morph
@@ -43,6 +44,7 @@ SANITIZERS = {
 }
 FILL = 0xA5
 TIME_LIMIT = 120                                # seconds for one child; a case takes well under one
+LONG_TIME_LIMIT = 600                           # ... but for the planes with a side of 65535: thousands of workgroups, about a minute
 REPORT = re.compile(r"Sanitizer|runtime error")
 
 
@@ -102,6 +104,7 @@ def run_case(programs, tmp_path, entry, scalars, tensors, expect=0):
     case = str(tmp_path / ("case%d.bin" % _serial[0]))
     _write_case(case, entry, scalars, tensors, expect)
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1")
+    limit = LONG_TIME_LIMIT if any(int(s) >= 65535 for s in scalars[1:3]) else TIME_LIMIT
     procs = {}
     for name, exe in programs.items():
         out = "%s.%s.out" % (case, name)
@@ -110,12 +113,12 @@ def run_case(programs, tmp_path, entry, scalars, tensors, expect=0):
     for name, (out, proc) in procs.items():
         what = "%s %s under %s" % (entry, list(scalars), name)
         try:
-            _stdout, stderr = proc.communicate(timeout=TIME_LIMIT)
+            _stdout, stderr = proc.communicate(timeout=limit)
         except subprocess.TimeoutExpired:       # a barrier that not every thread reaches: the emulation hangs where a GPU would not
             for _name, (_out, other) in procs.items():
                 other.kill()
                 other.communicate()
-            raise AssertionError("%s: no end after %d s" % (what, TIME_LIMIT))
+            raise AssertionError("%s: no end after %d s" % (what, limit))
         assert proc.returncode == 0 and not REPORT.search(stderr), "%s: exit status %d\n%s" % (what, proc.returncode, stderr[-6000:])
         blob = np.fromfile(out, np.uint8)
         got, at = {}, 0
@@ -169,6 +172,14 @@ def test_mask_morph(programs, tmp_path, shape):
 def test_mask_morph_behind_an_odd_byte(programs, tmp_path, mask_offset, out_offset):
     """Planes of 15 x 20 bytes: W is a multiple of 4, one pointer or both are not aligned, so the byte form must be the one chosen."""
     _morph(programs, tmp_path, make("blobs", 7, (3, 15, 20)), mask_offset, out_offset)
+
+
+@pytest.mark.parametrize("shape", LONG_THIN, ids=lambda s: "%dx%d" % s)
+def test_mask_morph_long_thin_planes(programs, tmp_path, shape):
+    """The sides of 65535 that tests/test_gpu_extents.py runs on the GPU, here first: one tile column of 1024 tile rows and its
+    transpose, one plane each (a workgroup is 256 host threads here: a thousand of them take half a minute); (65535, 4) takes
+    the dword form."""
+    _morph(programs, tmp_path, thin_masks(5 + shape[0] % 7, 1, *shape))
 
 
 # ---- boundary ------------------------------------------------------------------------------------------------------------------
@@ -238,6 +249,13 @@ def test_boundary_behind_unaligned_addresses(programs, tmp_path, offsets):
     m = class_blobs(3, (2, 40, 64), 3)
     for R in (2, 5):
         assert has_both(_boundary(programs, tmp_path, m, R, offsets=offsets))
+
+
+@pytest.mark.parametrize("shape", LONG_THIN, ids=lambda s: "%dx%d" % s)
+def test_boundary_long_thin_planes(programs, tmp_path, shape):
+    """The sides of 65535 of tests/test_gpu_extents.py at its two radii: the 8-px and the 32-px apron."""
+    for R in (5, 32):
+        assert has_both(_boundary(programs, tmp_path, thin_masks(5 + shape[0] % 7, 1, *shape), R))
 
 
 # ---- augment -------------------------------------------------------------------------------------------------------------------
@@ -333,6 +351,13 @@ def test_photometric(programs, tmp_path, H, W, C, n):
 def test_photometric_tile_seams(programs, tmp_path, H, W, C, n):
     img = random_images(H * W + C, n, H, W, C)
     _photometric(programs, tmp_path, img, gpu_photometric._rows(n, 3, 50), 3, 50)
+
+
+@pytest.mark.parametrize("H,W", PHOTOMETRIC_THIN, ids=lambda v: str(v))
+def test_photometric_long_thin_planes(programs, tmp_path, H, W, C=3):
+    """A side of 65535 beside the smallest side the op takes, as tests/test_gpu_extents.py runs it, one sample of three channels."""
+    img = random_images(3, 1, H, W, C)
+    _photometric(programs, tmp_path, img, gpu_photometric._rows(1, 7, 1000), 7, 1000)
 
 
 def test_photometric_saturation(programs, tmp_path):

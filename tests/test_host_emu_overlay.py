@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests import test_host_emu as emu
+from tests.extent_cases import LONG_THIN, thin_images, thin_masks
 from tests.test_host_emu import COMMON, SANITIZERS, run_case
 from tests.test_preview_host import blob_masks, dataset_lut, random_image, random_lut, rule_overlay
 
@@ -66,6 +67,13 @@ def test_thin_planes_and_tile_edges(programs, tmp_path, shape):
     """f = 1, two samples: of these only (16, 16), (64, 64) and (32, 128) take the dword form."""
     want = _overlay(programs, tmp_path, *_inputs(sum(shape), 2, *shape, 3))
     assert want.shape == (2 * shape[0], shape[1], 3)
+
+
+@pytest.mark.parametrize("shape", LONG_THIN, ids=lambda s: "%dx%d" % s)
+def test_long_thin_planes(programs, tmp_path, shape):
+    """The sides of 65535 that tests/test_gpu_extents.py runs on the GPU, here first; f = 1 is the one factor that divides them."""
+    H, W = shape
+    _overlay(programs, tmp_path, thin_images(5 + H % 7, 1, H, W, 3), thin_masks(5 + H % 7, 1, H, W), random_lut(5 + H % 7))
 
 
 @pytest.mark.parametrize("factor", FACTORS)

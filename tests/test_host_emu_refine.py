@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests import test_host_emu as emu
+from tests.extent_cases import LONG_THIN, thin_images, thin_masks
 from tests.test_host_emu import COMMON, SANITIZERS, run_case
 from tests.test_refine_host import THIN, TILE_EDGES, TABLE_BYTES, case, coarse_tables, every_value, expected, region_image
 
@@ -58,6 +59,14 @@ def test_thin_planes_and_tile_edges(programs, tmp_path, shape):
     """Two samples, three channels, three classes, radius 3; of these only (32, 64) takes the dword form."""
     H, W = shape
     _refine(programs, tmp_path, *case(H + W, 2, H, W), coarse_tables(), 3, 3, want_change=H * W > 1, want_tie=H * W > 1)
+
+
+@pytest.mark.parametrize("shape", LONG_THIN, ids=lambda s: "%dx%d" % s)
+def test_long_thin_planes(programs, tmp_path, shape):
+    """The sides of 65535 that tests/test_gpu_extents.py runs on the GPU, here first, with its radius 5: one tile column of 2048 tile
+    rows, and 1024 tiles in a row."""
+    H, W = shape
+    _refine(programs, tmp_path, thin_images(5 + H % 7, 1, H, W, 3), thin_masks(5 + H % 7, 1, H, W), coarse_tables(), 3, 5)
 
 
 @pytest.mark.parametrize("radius", [1, 2, 3, 4, 5])
