@@ -153,6 +153,9 @@ UNIT_SIGNATURES = {
     "csrc/gsa_scores.h": {
         "gsa_score_histogram": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     },
+    "csrc/gsa_resize.h": {
+        "gsa_pair_resize": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    },
 }
 
 

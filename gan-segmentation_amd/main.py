@@ -5,7 +5,11 @@ is out of scope.
 
 Writes ``img_%06d.jpg`` (RGB image; the reference flips to BGR only because cv2 expects it)
 and ``mask_%06d.png`` (single channel, class index) into BASE_DIR/dataset/train_generated, at R/f px with the additive
-key ``OUTPUT_DOWNSCALE: f`` (1, 2, 4 or 8; default 1).  The additive key ``MASK_MORPH: true`` (default false) cleans every mask on
+key ``OUTPUT_DOWNSCALE: f`` (1, 2, 4 or 8; default 1).  The additive key ``OUTPUT_SIZE`` (an int or ``[h, w]``, every side a
+multiple of 16, at most R/f and at least 1/16 of it; absent by default: off) then shrinks every pair on the GPU to that size
+(``resize_ops.resize_pair``: the image's exact area mean, the mask by the additive key ``OUTPUT_MASK_RESIZE``, "vote" -- the default, the
+class that covers most of the pixel; values 8..254 come out as 255 -- or "nearest"), after every mask filter below and before the files,
+``PAIR_STATS`` and the previews, which are then those of the resized pair.  The additive key ``MASK_MORPH: true`` (default false) cleans every mask on
 the GPU with the 5x5 close + open of reference utils.morph_mask before it is written (``mask_ops.morph_mask``).  The additive keys
 ``MASK_MIN_AREA: k`` (default 0: off), ``MASK_CONNECTIVITY`` (4 or 8, default 8) and ``MASK_FILL`` ("neighbour", the default, or
 0..255) replace every connected component of fewer than k pixels, after the morphology (``mask_ops.despeckle``).  The additive keys
@@ -88,6 +92,7 @@ def generate(cfg, limit=None, workers=None):
     from .image_generator import ImageGenerator
     from .pair_stats import check_pair_stats
     from .preview import check_preview_downscale, check_preview_every, write_previews
+    from .resize_ops import check_output_mask_resize, check_output_size, resize_pair
     from .seg_solver import SegSolver
     from .weights import GAN_MAX_RES_LOG2
 
@@ -117,6 +122,9 @@ def generate(cfg, limit=None, workers=None):
     mask_refine_radius = ImageGenerator.check_mask_refine_radius(cfg.get("MASK_REFINE_RADIUS", 3))
     mask_refine_sigma_space = ImageGenerator.check_mask_refine_sigma_space(cfg.get("MASK_REFINE_SIGMA_SPACE", 2.0))
     mask_refine_sigma_colour = ImageGenerator.check_mask_refine_sigma_colour(cfg.get("MASK_REFINE_SIGMA_COLOUR", 32.0))
+    # additive keys, checked here as well: the pair resized to any smaller size behind the filters (off by default)
+    output_size = check_output_size(cfg.get("OUTPUT_SIZE"), 2 ** GAN_MAX_RES_LOG2[gan] // downscale)
+    output_mask_resize = check_output_mask_resize(cfg.get("OUTPUT_MASK_RESIZE", "vote"))
     stats = check_pair_stats(cfg.get("PAIR_STATS", False))    # additive key, checked here as well: every rank writes its own shard file
     # additive keys, checked here as well: vis_%06d.jpg for the samples whose index is a multiple of k (off by default)
     preview_every = check_preview_every(cfg.get("PREVIEW_EVERY", 0))
@@ -148,6 +156,8 @@ def generate(cfg, limit=None, workers=None):
             for index, bs in shard_batches(n_generate, batch, world, rank):
                 # latents and noise keyed on the global sample index: the files are the same for any number of ranks
                 img, mask = netG.generate_indexed(index, bs, seed=seed)
+                if output_size is not None:
+                    img, mask = resize_pair(img, mask, output_size, output_mask_resize)
                 # the device-side checks travel with the batch: 8 bytes copied behind its kernels, read by the writer before it
                 # releases the batch's files -- a run of 10 000 samples stops at the first bad batch instead of reporting at close()
                 writer.submit(img, mask, index, status=netG.snapshot_status())

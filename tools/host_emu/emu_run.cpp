@@ -11,7 +11,8 @@
 //
 //   gsa-emu-case 1
 //   entry gsa_mask_morph            one of the four entries below (with -DGSA_EMU_OVERLAY and csrc/gsa_overlay.hip also gsa_overlay; with
-//                                   -DGSA_EMU_REFINE and csrc/gsa_refine.hip also gsa_mask_refine; either without the other)
+//                                   -DGSA_EMU_REFINE and csrc/gsa_refine.hip also gsa_mask_refine; with -DGSA_EMU_RESIZE and
+//                                   csrc/gsa_resize.hip also gsa_pair_resize; each without the others)
 //   expect 0                        the status the entry must return
 //   scalars 3 2 15 20               a count and the entry's integer arguments in order (decimal; 64-bit ones too)
 //   tensors 2                       a count and one line per pointer argument, in order:
@@ -42,6 +43,9 @@
 #endif
 #ifdef GSA_EMU_REFINE       // tests/test_host_emu_refine.py: gsa_refine.hip linked in, with or without the overlay
 #include "../../gan-segmentation_amd/csrc/gsa_refine.h"
+#endif
+#ifdef GSA_EMU_RESIZE       // tests/test_host_emu_resize.py: gsa_resize.hip linked in, with or without the other two
+#include "../../gan-segmentation_amd/csrc/gsa_resize.h"
 #endif
 
 namespace {
@@ -123,6 +127,11 @@ int main(int argc, char** argv) {
     } else if (entry == "gsa_mask_refine") {
         need(6, 4);     // n H W channels classes radius; img mask tables out
         status = gsa_mask_refine(nullptr, i32(0), i32(1), i32(2), i32(3), i32(4), i32(5), t[0].at(), t[1].at(), t[2].at(), t[3].at());
+#endif
+#ifdef GSA_EMU_RESIZE
+    } else if (entry == "gsa_pair_resize") {
+        need(7, 4);     // n H W C h w mask_mode; img mask img_out mask_out
+        status = gsa_pair_resize(nullptr, i32(0), i32(1), i32(2), i32(3), i32(4), i32(5), i32(6), t[0].at(), t[1].at(), t[2].at(), t[3].at());
 #endif
     } else {
         malformed("unknown entry");
