@@ -63,6 +63,8 @@ def api():
             "gsao_mapping_forward": (c.c_int, [vp, vp, i32, vp, vp]),
             "gsao_generator_forward_w": (c.c_int, [vp, vp, i32, vp, i32, pp, i32, vp, vp, pp, i32]),
             "gsao_generate_w": (c.c_int, [vp, vp, i32, vp, i32, pp, i32, vp, vp]),
+            "gsao_exact_headroom": (c.c_double, [vp, i32]),
+            "gsao_exact_operand_codes": (i32, [vp]),
             "gsao_version": (c.c_char_p, []),
         }
         for name, (res, args) in sig.items():
@@ -82,13 +84,15 @@ def _ptrs(arrays):
 class Oracle:
     """Generator + decoder on host memory in the canonical fp32 order (``precision="bf16"``: the bf16 mode's roundings)."""
 
-    def __init__(self, gcfg=None, gparams=None, dcfg=None, dparams=None, precision="fp32"):
+    def __init__(self, gcfg=None, gparams=None, dcfg=None, dparams=None, precision="fp32", witness=False):
         self.lib = api()
         self._h = ctypes.c_void_p()
         if self.lib.gsao_create(0, ctypes.byref(self._h)) != 0:
             raise OracleError("gsao_create failed")
         if precision != "fp32":
             self._check(self.lib.gsao_set_precision(self._h, {"bf16": 1}[precision]), "set_precision")
+        if witness:         # arms the exact-summation witness (it costs one more multiply-add per product in bf16 mode)
+            self.lib.gsao_exact_headroom(self._h, 1)
         self.gcfg, self.dcfg = gcfg, dcfg
         if gcfg is not None:
             cfg = _GenCfg(int(gcfg["max_res_log2"]), int(gcfg["fmap_base"]), float(gcfg["fmap_decay"]), int(gcfg["fmap_max"]),
@@ -167,6 +171,23 @@ class Oracle:
         self._check(self.lib.gsao_generate(self._h, None, n, z.ctypes.data, _ptrs(noise), len(noise), img.ctypes.data, mask.ctypes.data),
                     "generate")
         return img, mask
+
+    # -- exact-summation witness (bf16 mode; oracle/c/gsa_oracle.c wit_scan) -------------------------------------------------
+
+    def exact_headroom(self, reset=True):
+        """The smallest headroom, in bits, over the matrix-core accumulations (3x3 / stride-2 convolutions, decoder shortcut)
+        evaluated in bf16 mode since the last reset: 24 - log2(sum|a*w| / q), q a power of two that divides every product of
+        the call.  At > 0 every partial sum in every order is exact, so the HIP path must give the same bytes.  +inf if no
+        such accumulation ran (fp32 mode).  reset=True starts a new period.  Needs Oracle(..., witness=True)."""
+        h = float(self.lib.gsao_exact_headroom(self._h, 1 if reset else 0))
+        if h != h:
+            raise OracleError("the exact-summation witness is not armed: build the Oracle with witness=True")
+        return h
+
+    def exact_operand_codes(self):
+        """The smallest count of distinct bf16 codes among the activation operand tensors of the current witness period
+        (read it before exact_headroom() resets the period)."""
+        return int(self.lib.gsao_exact_operand_codes(self._h))
 
     # -- W space (include/gsa.h gsa_mapping_forward / gsa_generator_forward_w / gsa_generate_w) --------------------------
 

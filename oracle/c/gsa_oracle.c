@@ -121,6 +121,7 @@ typedef struct gsao_ctx {
     float* rgb_w; float* rgb_b;  /* [ch][C] effective, bias */
     /* decoder */
     int bf16;               /* gsao_set_precision: operands of the MFMA convolutions rounded to bf16 */
+    struct witness { double headroom; int codes, armed; } wit;    /* exact-summation witness (bf16 mode, once armed), see wit_scan() */
     int d_init, d_ready;
     int d_n, d_s0, d_bn, d_feat[MAX_LEVELS + 1], d_inch[MAX_LEVELS];
     param_table dp;
@@ -432,6 +433,8 @@ GSAO_API int gsao_create(int device, gsao_ctx** out) {
     (void)device;
     gsao_ctx* c = (gsao_ctx*)calloc(1, sizeof(gsao_ctx));
     if (!c) return fail(NULL, GSA_ERR_NOMEM, "out of memory%s (%ld)", "", 0);
+    c->wit.headroom = INFINITY;
+    c->wit.codes = INT32_MAX;
     *out = c;
     return GSA_OK;
 }
@@ -475,6 +478,19 @@ GSAO_API int gsao_set_precision(gsao_ctx* c, int32_t mode) {
     c->bf16 = mode;
     return GSA_OK;
 }
+
+/* The exact-summation witness (wit_scan() above): the smallest headroom in bits over the matrix-core accumulations this context
+ * evaluated in bf16 mode since the last reset (+inf if none ran, NaN if the witness was never armed).  reset != 0 starts a new period
+ * after reading; the first such call arms the witness. */
+GSAO_API double gsao_exact_headroom(gsao_ctx* c, int32_t reset) {
+    if (!c) return NAN;
+    const double h = c->wit.armed ? c->wit.headroom : NAN;
+    if (reset) { c->wit.headroom = INFINITY; c->wit.codes = INT32_MAX; c->wit.armed = 1; }
+    return h;
+}
+
+/* the smallest count of distinct bf16 codes among the activation operand tensors of the same period (INT32_MAX if none ran) */
+GSAO_API int32_t gsao_exact_operand_codes(const gsao_ctx* c) { return c ? c->wit.codes : -1; }
 
 GSAO_API const char* gsao_version(void) { return "gsa-oracle 0.1 (canonical fp32 CPU restatement)"; }
 
@@ -729,6 +745,67 @@ static inline float bf16r(float f) {
 }
 #define OPND(v) (bf ? bf16r(v) : (v))
 
+/* ---- Exact-summation witness (bf16 mode only; observes, never changes a value) ---------------------------------------
+ * The HIP path and this file differ, in bf16 mode, only in the order in which the matrix core adds the products of an
+ * accumulation.  If every product a*w of a call is a multiple of one power of two q and S = sum|a*w| < 2^24 * q for an
+ * output, every partial sum of that output in every order is a multiple of q below 2^24 * q: exactly representable in
+ * fp32, so the order cannot matter.  Per call of an accumulation the GPU runs on the matrix core (conv3x3 with perm = 1,
+ * deconv4x4s2, the decoder's 1x1 shortcut) the witness takes
+ *   q  = 2^(ea + ew), ea / ew the smallest exponent of the lowest set mantissa bit over the call's nonzero rounded
+ *        activations / weights (each operand is a multiple of its own lowest set bit, hence of the smallest one), and
+ *   S  = max over the outputs of sum|a*w| in double over the rounded operands (zero-padded taps add nothing),
+ * and keeps the minimum of  headroom = 24 - log2(S / q)  over all calls since the last reset, together with the smallest
+ * count of distinct bf16 codes among the activation operand tensors (a tensor on one or two codes would pin nothing).
+ * S costs one more multiply-add per product, so the witness sleeps until gsao_exact_headroom(ctx, 1) arms it: a context that never
+ * asks runs the plain loops, and asking an unarmed context answers NaN ("not measured"), never a value that reads as "exact". */
+typedef struct witness witness;
+
+static int low_bit_exp(float v) {      /* v != 0, finite: exponent e of the lowest set bit, v = odd * 2^e */
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    const int ef = (int)((u >> 23) & 0xff);
+    const uint32_t m = ef ? ((u & 0x7fffffu) | 0x800000u) : (u & 0x7fffffu);
+    return (ef ? ef : 1) - 150 + __builtin_ctz(m);
+}
+
+/* smallest low_bit_exp over the nonzero bf16-rounded values of x (INT32_MAX if all are zero); codes: distinct bf16 codes */
+static int wit_scan(const float* x, size_t n, int* codes) {
+    int e = INT32_MAX;
+    uint32_t* seen = codes ? (uint32_t*)calloc(2048, sizeof(uint32_t)) : NULL;
+    for (size_t i = 0; i < n; ++i) {
+        const float v = bf16r(x[i]);
+        if (seen) { uint32_t u; memcpy(&u, &v, 4); seen[u >> 21] |= 1u << ((u >> 16) & 31); }
+        if (v != 0.0f && isfinite(v)) { const int k = low_bit_exp(v); if (k < e) e = k; }
+    }
+    if (seen) {
+        int cnt = 0;
+        for (int i = 0; i < 2048; ++i) cnt += __builtin_popcount(seen[i]);
+        *codes = cnt;
+        free(seen);
+    }
+    return e;
+}
+
+static void wit_codes(witness* wt, const float* a, size_t na) {
+    int codes;
+    (void)wit_scan(a, na, &codes);
+    if (codes < wt->codes) wt->codes = codes;
+}
+
+/* q exponent of a call from its operand tensors; notes the activation tensor's code count */
+static int wit_open(witness* wt, const float* a, size_t na, const float* w, size_t nw) {
+    int codes;
+    const int ea = wit_scan(a, na, &codes), ew = wit_scan(w, nw, NULL);
+    if (codes < wt->codes) wt->codes = codes;
+    return (ea == INT32_MAX || ew == INT32_MAX) ? INT32_MAX : ea + ew;
+}
+
+static void wit_close(witness* wt, double smax, int qe) {
+    if (qe == INT32_MAX || !(smax > 0.0)) return;       /* all products zero: nothing to order */
+    const double h = 24.0 - (log2(smax) - (double)qe);
+    if (h < wt->headroom) wt->headroom = h;
+}
+
 /* bf16 mode, round 2: every activation tensor that lives in HBM is bf16 -- the producer rounds what it stores (statistics
  * are taken from the fp32 values first), consumers widen exactly */
 static void store_bf16(float* x, size_t n, int bf) {
@@ -747,16 +824,21 @@ static void store_bf16(float* x, size_t n, int bf) {
  * 4^2-32^2 were ONE dependent chain of 1152 MFMAs behind 32 load -> LDS -> barrier rounds before. */
 static int use_ksplit(int Cin, int H, int Cout) { return Cin >= 64 && Cin % 64 == 0 && (H <= 8 || (H <= 32 && Cout <= 32)); }
 
-static void conv3x3(const float* in, int Hs, int Ws, int Cin, int up, const float* Wp, int Cout, float* out, int bf, int perm) {
+static void conv3x3(const float* in, int Hs, int Ws, int Cin, int up, const float* Wp, int Cout, float* out, int bf, int perm, witness* wt) {
     const int H = Hs << up, W = Ws << up;
     const int nblk = Cin / CB;
     const int nq = (perm && use_ksplit(Cin, H, Cout)) ? 4 : 1, bq = nblk / nq;      /* perm = 0: the final conv (vector ALU): one chain */
-#pragma omp parallel for schedule(dynamic, 1)
+    if (!(bf && perm) || !wt || !wt->armed) wt = NULL;
+    const int qe = wt ? wit_open(wt, in, (size_t)Hs * Ws * Cin, Wp, (size_t)9 * Cin * Cout) : 0;
+    double smax = 0.0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(max : smax)
     for (int y = 0; y < H; ++y)
         for (int x0 = 0; x0 < W; x0 += PX)
             for (int o0 = 0; o0 < Cout; o0 += OC) {
                 const int on = Cout - o0 < OC ? Cout - o0 : OC;
                 float part[4][PX][OC];
+                double sab[PX][OC];
+                if (wt) memset(sab, 0, sizeof sab);
                 for (int q = 0; q < nq; ++q) {
                     float (*acc)[OC] = part[q];
                     for (int p = 0; p < PX; ++p)
@@ -781,6 +863,10 @@ static void conv3x3(const float* in, int Hs, int Ws, int Cin, int up, const floa
                                         } else {
                                             for (int o = 0; o < on; ++o) acc[p][o] = fmaf(a, wrow[o], acc[p][o]);
                                         }
+                                        if (wt) {
+                                            const double aa = fabs((double)a);
+                                            for (int o = 0; o < OC; ++o) sab[p][o] = fma(aa, fabs((double)wrow[o]), sab[p][o]);
+                                        }
                                     }
                                 }
                         }
@@ -789,21 +875,30 @@ static void conv3x3(const float* in, int Hs, int Ws, int Cin, int up, const floa
                     for (int o = 0; o < on; ++o)
                         out[((size_t)y * W + x0 + p) * Cout + o0 + o] =
                             nq == 4 ? (part[0][p][o] + part[1][p][o]) + (part[2][p][o] + part[3][p][o]) : part[0][p][o];
+                if (wt)
+                    for (int p = 0; p < PX; ++p)
+                        for (int o = 0; o < on; ++o) if (sab[p][o] > smax) smax = sab[p][o];
             }
+    if (wt) wit_close(wt, smax, qe);
 }
 
 /* Deconvolution k4 s2 p1 (reference networks_stylegan.py:460-476, A.3):
  * out[oy][ox][o] = sum in[iy][ix][i] * W[i][o][ky][kx] over oy = 2*iy - 1 + ky.
  * Canonical order: 16-channel block, then valid ky ascending, valid kx ascending, channel. */
-static void deconv4x4s2(const float* in, int Hs, int Ws, int Cin, const float* Wd, int Cout, float* out, int bf) {
+static void deconv4x4s2(const float* in, int Hs, int Ws, int Cin, const float* Wd, int Cout, float* out, int bf, witness* wt) {
     const int H = Hs * 2, W = Ws * 2;
-#pragma omp parallel for schedule(dynamic, 1)
+    if (!bf || !wt->armed) wt = NULL;
+    const int qe = wt ? wit_open(wt, in, (size_t)Hs * Ws * Cin, Wd, (size_t)16 * Cin * Cout) : 0;
+    double smax = 0.0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(max : smax)
     for (int oy = 0; oy < H; ++oy)
         for (int ox = 0; ox < W; ++ox)
             for (int o0 = 0; o0 < Cout; o0 += OC) {
                 const int on = Cout - o0 < OC ? Cout - o0 : OC;
                 float acc[OC];
+                double sab[OC];
                 for (int o = 0; o < OC; ++o) acc[o] = 0.0f;
+                if (wt) memset(sab, 0, sizeof sab);
                 for (int cb = 0; cb < Cin / CB; ++cb)
                     for (int ky = (oy + 1) & 1; ky < 4; ky += 2) {
                         const int iy = (oy + 1 - ky) / 2;
@@ -816,11 +911,18 @@ static void deconv4x4s2(const float* in, int Hs, int Ws, int Cin, const float* W
                                 const float a = OPND(in[((size_t)iy * Ws + ix) * Cin + cb * CB + ci]);
                                 const float* wrow = Wd + (((size_t)cb * 16 + ky * 4 + kx) * CB + ci) * Cout + o0;
                                 for (int o = 0; o < on; ++o) acc[o] = fmaf(a, OPND(wrow[o]), acc[o]);
+                                if (wt) {
+                                    const double aa = fabs((double)a);
+                                    for (int o = 0; o < on; ++o) sab[o] = fma(aa, fabs((double)OPND(wrow[o])), sab[o]);
+                                }
                             }
                         }
                     }
                 for (int o = 0; o < on; ++o) out[((size_t)oy * W + ox) * Cout + o0 + o] = acc[o];
+                if (wt)
+                    for (int o = 0; o < on; ++o) if (sab[o] > smax) smax = sab[o];
             }
+    if (wt) wit_close(wt, smax, qe);
 }
 
 /* ---- Winograd F(2x2, 2x2) form of the stride-2 layers (round 3) --------------------------------------------------
@@ -1087,16 +1189,16 @@ static int synthesis(gsao_ctx* c, int32_t n, const float* z, const float* dlat, 
                     } else {
                         /* xb holds the affine-applied previous feature */
                         if ((B->is_deconv || R >= 16) && use_wino22(c->bf16)) deconv4x4s2_wino(xb, R / 2, R / 2, Cin, B->w1, C, xc);
-                        else if (B->is_deconv) deconv4x4s2(xb, R / 2, R / 2, Cin, B->w1, C, xc, c->bf16);
-                        else if (R >= 16) deconv4x4s2(xb, R / 2, R / 2, Cin, B->w1, C, xc, c->bf16);   /* sub-pixel up+conv */
-                        else conv3x3(xb, R / 2, R / 2, Cin, 1, B->w1, C, xc, c->bf16, 1);
+                        else if (B->is_deconv) deconv4x4s2(xb, R / 2, R / 2, Cin, B->w1, C, xc, c->bf16, &c->wit);
+                        else if (R >= 16) deconv4x4s2(xb, R / 2, R / 2, Cin, B->w1, C, xc, c->bf16, &c->wit);   /* sub-pixel up+conv */
+                        else conv3x3(xb, R / 2, R / 2, Cin, 1, B->w1, C, xc, c->bf16, 1, &c->wit);
                         store_bf16(xc, npix * C, c->bf16);      /* the raw conv_1 output is a stored tensor */
                         blur3x3(xc, R, R, C, B->blur, xa);
                     }
                 } else {
                     if (use_wino43(R, R, C, C, c->bf16)) conv3x3_wino43(xb, R, R, C, B->w2u, C, xa);
                     else if (use_wino(R, R, C, 0, c->bf16)) conv3x3_wino(xb, R, R, C, B->w2u, C, xa);
-                    else conv3x3(xb, R, R, C, 0, B->w2, C, xa, c->bf16, 1);
+                    else conv3x3(xb, R, R, C, 0, B->w2, C, xa, c->bf16, 1, &c->wit);
                 }
                 noise_bias_act(xa, R, R, C, nz, B->nscale[k], B->nbias[k]);
                 plane_stats(xa, R, R, C, I1, I2);
@@ -1306,7 +1408,7 @@ GSAO_API int gsao_decoder_forward(gsao_ctx* c, void* stream, int32_t n, const fl
             /* cvt_block: conv3x3+bias -> BN -> LeakyReLU -> Dropout(identity), reference networks_seg.py:64-79 */
             if (use_wino43(R, R, d->I, d->F, c->bf16)) conv3x3_wino43(fin, R, R, d->I, d->cvt_u, d->F, ya);
             else if (use_wino(R, R, d->F, 0, c->bf16)) conv3x3_wino(fin, R, R, d->I, d->cvt_u, d->F, ya);
-            else conv3x3(fin, R, R, d->I, 0, d->cvt_w, d->F, ya, c->bf16, 1);
+            else conv3x3(fin, R, R, d->I, 0, d->cvt_w, d->F, ya, c->bf16, 1, &c->wit);
             bias_bn_act(ya, npix, d->F, d->cvt_b, d->cvt_s, d->cvt_rm, d->cvt_beta);
             store_bf16(ya, npix * d->F, c->bf16);
             /* concat(prev, cvt) on channels, reference :108-109 */
@@ -1323,14 +1425,17 @@ GSAO_API int gsao_decoder_forward(gsao_ctx* c, void* stream, int32_t n, const fl
                 const int R2 = 2 * R;
                 const size_t np2 = (size_t)R2 * R2;
                 if (R2 >= 16 && use_wino22(c->bf16)) deconv4x4s2_wino(cat, R, R, d->in_c, d->a_w, d->cs, ya);
-                else if (R2 >= 16) deconv4x4s2(cat, R, R, d->in_c, d->a_w, d->cs, ya, c->bf16);   /* sub-pixel up+conv */
-                else conv3x3(cat, R, R, d->in_c, 1, d->a_w, d->cs, ya, c->bf16, 1);
+                else if (R2 >= 16) deconv4x4s2(cat, R, R, d->in_c, d->a_w, d->cs, ya, c->bf16, &c->wit);   /* sub-pixel up+conv */
+                else conv3x3(cat, R, R, d->in_c, 1, d->a_w, d->cs, ya, c->bf16, 1, &c->wit);
                 bias_bn_act(ya, np2, d->cs, d->a_b, d->a_s, d->a_rm, d->a_beta);
                 store_bf16(ya, np2 * d->cs, c->bf16);
                 if (use_wino(R2, R2, d->cs, 0, c->bf16)) conv3x3_wino(ya, R2, R2, d->cs, d->b_u, d->cs, yb);
-                else conv3x3(ya, R2, R2, d->cs, 0, d->b_w, d->cs, yb, c->bf16, 1);
+                else conv3x3(ya, R2, R2, d->cs, 0, d->b_w, d->cs, yb, c->bf16, 1, &c->wit);
                 bias_bn_act(yb, np2, d->cs, d->b_b, d->b_s, d->b_rm, d->b_beta);
-#pragma omp parallel for schedule(static)
+                witness* wt = (c->bf16 && c->wit.armed && d->has_sc) ? &c->wit : NULL;
+                const int qe = wt ? wit_open(wt, cat, npix * d->in_c, d->sc_w, (size_t)d->in_c * d->cs) : 0;
+                double smax = 0.0;
+#pragma omp parallel for schedule(static) reduction(max : smax)
                 for (int y = 0; y < R2; ++y)
                     for (int x = 0; x < R2; ++x) {
                         const float* src = cat + ((size_t)(y >> 1) * R + (x >> 1)) * d->in_c;
@@ -1340,11 +1445,14 @@ GSAO_API int gsao_decoder_forward(gsao_ctx* c, void* stream, int32_t n, const fl
                             float sc;
                             if (d->has_sc) {
                                 float acc = 0.0f;
+                                double sab = 0.0;
                                 const int bf = c->bf16;
                                 for (int k0 = 0; k0 < d->in_c; ++k0) {      /* the MFMA order of the 16-channel blocks */
                                     const int ch = (k0 & ~15) | CPERM(k0 & 15);
                                     acc = fmaf(OPND(src[ch]), OPND(d->sc_w[(size_t)ch * d->cs + o]), acc);
+                                    if (wt) sab = fma(fabs((double)OPND(src[ch])), fabs((double)OPND(d->sc_w[(size_t)ch * d->cs + o])), sab);
                                 }
+                                if (sab > smax) smax = sab;
                                 sc = acc + d->sc_b[o];
                                 if (c->bf16) sc = bf16r(sc);       /* the shortcut is a stored tensor of its own */
                             } else {
@@ -1354,10 +1462,12 @@ GSAO_API int gsao_decoder_forward(gsao_ctx* c, void* stream, int32_t n, const fl
                             if (c->bf16) dst[o] = bf16r(dst[o]);
                         }
                     }
+                if (wt) wit_close(wt, smax, qe);
             } else {
                 /* final conv3x3 + bias -> logits, then argmax (first maximum), reference :91-92, seg_solver.py:326 */
                 const int nc = d->cs;
-                conv3x3(cat, R, R, d->in_c, 0, d->f_w, nc, ya, 0, 0);   /* final conv: fp32 in both modes, ascending channel order */
+                if (c->bf16 && c->wit.armed) wit_codes(&c->wit, cat, npix * d->in_c);      /* the last stored activation: the final conv's operand */
+                conv3x3(cat, R, R, d->in_c, 0, d->f_w, nc, ya, 0, 0, NULL);   /* final conv: fp32 in both modes, ascending channel order */
                 for (size_t p = 0; p < npix; ++p) {
                     int best = 0;
                     float bv = 0.0f;

@@ -1,5 +1,10 @@
 """GPU tests of the bf16-MFMA mode (BASELINE.json configs[4]: "bf16 MFMA", fp32 accumulate and statistics).
 
+Two contracts hold in this mode.  On exactly summable models -- every matrix-core accumulation made of multiples of one power of two q
+with sum|a*w| < 2^22 q, which tests/test_exact_bf16_host.py asserts on the oracle alone (Oracle.exact_headroom() >= 2 bits) -- no order of
+summation can change a bit, and tests/test_gpu_bf16_exact.py holds every tensor of every level to the bf16 oracle's bytes.  On general
+weights, which this module uses, parity is a tolerance:
+
 Tolerance contract (stated here, loosened from the fp32 path's bit equality / 1e-3):
  * the arithmetic differs from fp32 in the operands of the MFMA convolutions (inputs after AdaIN and weights rounded to
    bf16, 8 significant bits) and -- round 2 -- in the activation tensors that live in HBM, which are bf16 too (the producer
