@@ -156,6 +156,10 @@ UNIT_SIGNATURES = {
     "csrc/gsa_resize.h": {
         "gsa_pair_resize": (_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     },
+    "csrc/gsa_region.h": {
+        "gsa_region_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+        "gsa_region_tversky": (_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _f32, _f32, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    },
 }
 
 

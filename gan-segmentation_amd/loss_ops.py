@@ -6,7 +6,11 @@ and the config key ``TRAIN_LOSS`` train the decoder with.  Without a spec nothin
 ``LossSpec`` holds the options and validates them, ``boundary_weight_table`` is the weight of a pixel by its squared distance to the
 nearest label boundary, ``class_weights_from_masks`` computes the two class-weight vectors of ``pair_stats.summarise`` from
 annotation masks, and ``softmax_loss`` enqueues the two kernels on the current stream of the logits' device.  Results are the same
-bits from run to run and do not depend on the batch a sample is in.  No CPU fallback."""
+bits from run to run and do not depend on the batch a sample is in.  No CPU fallback.
+
+``region_loss`` is the region term beside them (csrc/gsa_region.h, csrc/gsa_region.hip): per sample and class
+the soft Tversky index of the softmax against the labels -- soft Dice, soft Jaccard -- with its loss and gradient, which
+``LossSpec(region=...)`` adds to the cross-entropy term of a training step."""
 import math
 
 import numpy as np
@@ -23,8 +27,16 @@ MIN_CLASSES, MAX_CLASSES = 2, 64
 MAX_GAMMA = 8.0
 MAX_RADIUS = 32             # mask_ops.BOUNDARY_MAX_RADIUS: radius^2 <= 1024 = LOSS_TABLE - 2
 CLASS_WEIGHT_SCHEMES = ("median", "inverse")
-SPEC_KEYS = ("gamma", "normalise", "class_weights", "boundary")
+SPEC_KEYS = ("gamma", "normalise", "class_weights", "boundary", "region")
 BOUNDARY_KEYS = ("weight", "sigma", "radius")
+# csrc/gsa_region.h
+REGION_MAX_CLASSES = 16     # classes of the region term: 2 .. 16
+REGION_MAX_BLOCKS = 512     # workgroups that walk one sample
+REGION_SUMS = 3
+SUM_I, SUM_P, SUM_G = range(REGION_SUMS)            # rows of the region ``sums``: intersection, predicted mass, labelled pixels
+REGION_CLASSES = {"present": 0, "all": 1}
+REGION_KEYS = ("weight", "alpha", "beta", "smooth", "classes")
+REGION_DEFAULTS = {"alpha": 0.5, "beta": 0.5, "smooth": 1.0, "classes": "present"}
 
 
 def _number(v):
@@ -86,6 +98,39 @@ def check_boundary(v, what="boundary"):
     return {"weight": float(w), "sigma": float(s), "radius": int(r)}
 
 
+def check_tversky(alpha, beta, smooth, classes, what="region"):
+    """alpha, beta and smooth as floats >= 0 with alpha + beta > 0, and the name of the class set, "present" or "all".  ValueError
+    otherwise, naming the argument."""
+    for name, v in (("alpha", alpha), ("beta", beta), ("smooth", smooth)):
+        if not _number(v) or float(v) < 0.0:
+            raise ValueError("%s: %s must be a number >= 0, got %r" % (what, name, v))
+    if float(alpha) + float(beta) == 0.0:
+        raise ValueError("%s: alpha + beta must be > 0, got alpha %r and beta %r" % (what, alpha, beta))
+    if not isinstance(classes, str) or classes not in REGION_CLASSES:
+        raise ValueError("%s: classes must be one of %s, got %r" % (what, ", ".join(repr(k) for k in REGION_CLASSES), classes))
+    return float(alpha), float(beta), float(smooth), classes
+
+
+def check_region(v, what="region"):
+    """None, or a mapping with the key weight (>= 0) and keys among alpha, beta (>= 0, not both 0; default 0.5: soft Dice), smooth
+    (>= 0, default 1) and classes ("present", the default, or "all") -> None or a dict of all five.  ValueError otherwise, naming
+    the key."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError("%s must be a mapping with keys among %s, got %r" % (what, ", ".join(REGION_KEYS), v))
+    unknown = sorted(str(k) for k in v if k not in REGION_KEYS)
+    missing = [k for k in ("weight",) if k not in v]
+    if unknown or missing:
+        raise ValueError("%s: %s" % (what, "; ".join(([("unknown key %s" % k) for k in unknown]) + [("missing key %s" % k) for k in missing])))
+    w = v["weight"]
+    if not _number(w) or float(w) < 0.0:
+        raise ValueError("%s: weight must be a number >= 0, got %r" % (what, w))
+    o = dict(REGION_DEFAULTS, **{k: v[k] for k in REGION_KEYS[1:] if k in v})
+    alpha, beta, smooth, classes = check_tversky(o["alpha"], o["beta"], o["smooth"], o["classes"], what)
+    return {"weight": float(w), "alpha": alpha, "beta": beta, "smooth": smooth, "classes": classes}
+
+
 def boundary_weight_table(radius, weight, sigma):
     """float32[LOSS_TABLE]: the weight of a pixel by the squared distance d to the nearest pixel of another label, as
     ``mask_ops.boundary_distance`` gives it: 1 + weight * exp(-d / (2 sigma^2)) for 1 <= d <= radius^2, and exactly 1 for d = 0 (no
@@ -103,14 +148,16 @@ class LossSpec:
     "mean" (over H * W, the reference's SoftmaxCELoss), "valid" (over the sum of the weights) or "focal" (over the sum of the weights
     times the focal factor: the reference's NormalizedFocalLossSoftmax); ``class_weights``: None, ``num_classes`` numbers >= 0, or
     "median" / "inverse", which ``SegSolver.fit`` computes from its annotation masks (``with_class_weights``);
-    ``boundary``: None or ``dict(weight=, sigma=, radius=)``, the per-pixel factor of ``boundary_weight_table``.  ValueError on
-    anything else, the message beginning with ``what``."""
+    ``boundary``: None or ``dict(weight=, sigma=, radius=)``, the per-pixel factor of ``boundary_weight_table``; ``region``: None or
+    ``dict(weight=, alpha=, beta=, smooth=, classes=)`` (``check_region``): ``weight`` times the region term of ``region_loss`` is
+    added to the loss, with the spec's numeric class weights.  ValueError on anything else, the message beginning with ``what``."""
 
-    def __init__(self, gamma=0.0, normalise="mean", class_weights=None, boundary=None, what="LossSpec"):
+    def __init__(self, gamma=0.0, normalise="mean", class_weights=None, boundary=None, region=None, what="LossSpec"):
         self.gamma = check_gamma(gamma, "%s: gamma" % what)
         self.normalise = check_normalise(normalise, "%s: normalise" % what)
         self.class_weights = check_class_weights(class_weights, "%s: class_weights" % what)
         self.boundary = check_boundary(boundary, "%s: boundary" % what)
+        self.region = check_region(region, "%s: region" % what)
 
     @classmethod
     def from_mapping(cls, v, what="loss"):
@@ -129,7 +176,7 @@ class LossSpec:
 
     def with_class_weights(self, weights):
         """A copy with ``class_weights`` replaced by numbers."""
-        return LossSpec(self.gamma, self.normalise, weights, self.boundary)
+        return LossSpec(self.gamma, self.normalise, weights, self.boundary, self.region)
 
     def table(self):
         """``boundary_weight_table`` of the spec's boundary, or None."""
@@ -138,7 +185,8 @@ class LossSpec:
     def as_dict(self):
         return {"gamma": self.gamma, "normalise": self.normalise,
                 "class_weights": list(self.class_weights) if isinstance(self.class_weights, tuple) else self.class_weights,
-                "boundary": dict(self.boundary) if self.boundary else None}
+                "boundary": dict(self.boundary) if self.boundary else None,
+                "region": dict(self.region) if self.region else None}
 
     def __repr__(self):
         return "LossSpec(%s)" % ", ".join("%s=%r" % kv for kv in self.as_dict().items())
@@ -268,3 +316,68 @@ def softmax_loss(logits, labels, spec=None, gamma=0.0, normalise="mean", class_w
                NORMALISE[normalise], float(grad_scale), workspace.data_ptr(), sums.data_ptr(), loss.data_ptr(),
                dlogits.data_ptr() if grad else None)
     return loss, sums, dlogits
+
+
+def region_workspace_bytes(n, classes, HW):
+    """gsa_region_workspace_bytes: n * min(ceil(HW / 256), REGION_MAX_BLOCKS) * 3 * classes * 8."""
+    size = _lib.load_library().fn("gsa_region_workspace_bytes")(int(n), int(classes), int(HW))
+    if size < 0:
+        raise ValueError("no workspace for n = %r, classes = %r, HW = %r" % (n, classes, HW))
+    return int(size)
+
+
+def region_loss(logits, labels, alpha=0.5, beta=0.5, smooth=1.0, classes="present", class_weights=None, grad=True, grad_scale=1.0,
+                into=None, workspace=None):
+    """The region term of csrc/gsa_region.h: per sample the weighted mean over the chosen classes of 1 - TI_k, TI_k the soft
+    Tversky index of the softmax against the labels (alpha = beta = 0.5: soft Dice; alpha = beta = 1: soft Jaccard; alpha weighs
+    false positives, beta false negatives; ``smooth`` is added to numerator and denominator).
+    logits (n, K, H, W) or (n, K, HW) contiguous float32 CUDA tensor, K in 2..16; labels: a contiguous int8 tensor of n * HW
+    elements on the same device, a pixel being valid iff its label is in 0 .. K - 1.  ``classes``: "present" (the classes that a
+    valid pixel of the sample has) or "all"; ``class_weights``: K numbers or a float32 device tensor of them.  ``grad=False``:
+    forward only.  ``into``: a gradient tensor like logits to accumulate into with one fp32 add an element -- the ``dlogits`` of
+    ``softmax_loss``, say; it is returned as dlogits, and ignored pixels keep their bits.  ``workspace``: a uint8 device tensor of at
+    least ``region_workspace_bytes(n, K, HW)`` bytes to reuse, else one is allocated.
+    -> (loss float32 (n,), sums float64 (n, 3, K) = [I, P, G], index float32 (n, K) = TI_k, 0 for a class outside the set, dlogits
+    as logits or None); dlogits = grad_scale * d loss[n] / d logits.  Two kernels on the current stream of the logits' device;
+    ValueError on anything else; no CPU fallback."""
+    import torch
+    from ._runtime import is_device_tensor, launch
+    if not is_device_tensor(logits, torch.float32, dims=(3, 4)):
+        raise ValueError("logits must be a contiguous float32 CUDA tensor (n, K, H, W) or (n, K, HW)")
+    n, K = int(logits.shape[0]), int(logits.shape[1])
+    HW = int(np.prod(logits.shape[2:]))
+    dev = logits.device
+    if not MIN_CLASSES <= K <= REGION_MAX_CLASSES or HW <= 0:
+        raise ValueError("logits must hold %d..%d classes and at least one pixel, got shape %s"
+                         % (MIN_CLASSES, REGION_MAX_CLASSES, tuple(logits.shape)))
+    if n * K * HW >= 2 ** 40:
+        raise ValueError("logits of %d elements: at most 2^40 - 1" % (n * K * HW))
+    if not is_device_tensor(labels, torch.int8, device=dev) or labels.numel() != n * HW:
+        raise ValueError("labels must be a contiguous int8 tensor of %d elements on %s" % (n * HW, dev))
+    alpha, beta, smooth, classes = check_tversky(alpha, beta, smooth, classes, "region_loss")
+    if not _number(grad_scale):
+        raise ValueError("grad_scale must be a finite number, got %r" % (grad_scale,))
+    cw = None
+    if class_weights is not None:
+        if not isinstance(class_weights, torch.Tensor):
+            class_weights = check_class_weights(class_weights, num_classes=K, schemes=False)
+        cw = _device_f32(class_weights, K, dev, "class_weights")
+    if into is not None:
+        if not grad:
+            raise ValueError("into needs grad=True")
+        if not is_device_tensor(into, torch.float32, shape=logits.shape, device=dev):
+            raise ValueError("into must be a contiguous float32 tensor of shape %s on %s" % (tuple(logits.shape), dev))
+    loss = torch.empty(n, device=dev, dtype=torch.float32)
+    sums = torch.empty((n, REGION_SUMS, K), device=dev, dtype=torch.float64)
+    index = torch.empty((n, K), device=dev, dtype=torch.float32)
+    dlogits = (into if into is not None else torch.empty_like(logits)) if grad else None
+    if n:
+        need = region_workspace_bytes(n, K, HW)
+        if workspace is None:
+            workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+        elif not is_device_tensor(workspace, torch.uint8, device=dev) or workspace.numel() < need or workspace.data_ptr() % 8:
+            raise ValueError("workspace must be a contiguous, 8-byte aligned uint8 tensor of at least %d bytes on %s" % (need, dev))
+        launch("gsa_region_tversky", dev, n, K, HW, logits.data_ptr(), labels.data_ptr(), cw.data_ptr() if cw is not None else None,
+               alpha, beta, smooth, REGION_CLASSES[classes], float(grad_scale), 1 if into is not None else 0, workspace.data_ptr(),
+               sums.data_ptr(), index.data_ptr(), loss.data_ptr(), dlogits.data_ptr() if grad else None)
+    return loss, sums, index, dlogits

@@ -39,9 +39,11 @@ margins (``SegSolver.evaluate_scores``, csrc/gsa_scores.h); the additive key ``E
 per logit unit.
 `train` takes the additive key ``TRAIN_LOSS`` (a mapping with keys among ``gamma``: 0 or 1..8, the focal exponent; ``normalise``:
 "mean", "valid" or "focal"; ``class_weights``: a list of one number per class, or "median" / "inverse", computed from the annotation
-masks under BASE_DIR/data; ``boundary``: a mapping with ``weight``, ``sigma`` and ``radius``, 1..32 px; absent by default: the
+masks under BASE_DIR/data; ``boundary``: a mapping with ``weight``, ``sigma`` and ``radius``, 1..32 px; ``region``: a mapping with
+``weight`` and optionally ``alpha``, ``beta``, ``smooth`` and ``classes``, such as ``{weight: 1.0, alpha: 0.3, beta: 0.7}``, which adds
+weight times the soft Tversky (Dice, Jaccard) loss of csrc/gsa_region.h; absent by default: the
 reference's loss and nothing else) and trains the decoder with the loss of ``loss_ops`` (csrc/gsa_loss.h), the epoch lines then
-carrying the mean T/B as well.
+carrying the mean T/B as well, and with a region term the mean index of every class.
 With torchrun (one process per GPU) the sample indices are sharded across ranks and every rank
 writes its own files -- no collective is needed when the sink is the filesystem.
 """
@@ -208,8 +210,9 @@ def _solver(cfg, keep_weights=False):
 
 def check_train_loss(v):
     """The TRAIN_LOSS key: None (absent: the reference's loss), or a mapping with keys among gamma (0 or 1..8), normalise ("mean",
-    "valid" or "focal"), class_weights (a list of numbers, "median" or "inverse") and boundary (a mapping with weight, sigma and
-    radius) -> None or a ``loss_ops.LossSpec``.  ValueError otherwise, the message naming the key."""
+    "valid" or "focal"), class_weights (a list of numbers, "median" or "inverse"), boundary (a mapping with weight, sigma and
+    radius) and region (a mapping with weight and, optionally, alpha, beta, smooth and classes: ``loss_ops.check_region``)
+    -> None or a ``loss_ops.LossSpec``.  ValueError otherwise, the message naming the key."""
     from . import loss_ops
     if v is None:
         return None

@@ -103,7 +103,8 @@ class SegSolver:
         class_weights, boundary; ValueError on anything else, before a sample is read).  ``class_weights`` "median" or "inverse" are
         computed on the host from the annotation masks of ``path_to_data`` (``loss_ops.class_weights_from_masks``; a class that no
         mask holds gets weight 1: no pixel uses it).  With a spec the log line also carries the epoch's mean T/B, valid pixels over
-        focal mass (the reference's ``_k_sum``)."""
+        focal mass (the reference's ``_k_sum``), and with a region term of weight > 0 after it the epoch's mean Tversky index of
+        every class, ``TI=`` and one figure a class."""
         import random
         from . import annotation_io, loss_ops
         from .trainer import DecoderTrainer
@@ -145,7 +146,7 @@ class SegSolver:
             rng.shuffle(order)           # the same permutation on every rank (same seed) ...
             if world > 1:                           # ... of which rank r takes every world-th sample: the trainer
                 order = order[:len(order) - len(order) % world][rank::world]   # all-reduces the gradients, so a step sees `world` samples
-            total, ratios = 0.0, []
+            total, ratios, indices = 0.0, [], []
             for fname in order:
                 image_id = int(os.path.splitext(fname)[0].split("_")[-1])
                 mask, _img, feats = annotation_io.load_sample(self.path_to_data, image_id)
@@ -154,12 +155,17 @@ class SegSolver:
                 total += tr.step(feats, mask[None])
                 if spec is not None:
                     ratios.append(tr.last_sums)     # on the device: read once an epoch
+                    if tr.last_region is not None:
+                        indices.append(tr.last_region)
             history.append(total / len(order))
             if log is not None and spec is not None:
                 sums = torch.cat(ratios).cpu().numpy()
                 live = sums[:, loss_ops.SUM_B] > 0
                 t_over_b = float(np.mean(sums[live, loss_ops.SUM_T] / sums[live, loss_ops.SUM_B])) if live.any() else 0.0
-                log("Epoch[%d] Train-total-loss=%f T/B=%f" % (epoch + 1, history[-1], t_over_b))
+                line = "Epoch[%d] Train-total-loss=%f T/B=%f" % (epoch + 1, history[-1], t_over_b)
+                if indices:
+                    line += " TI=" + ",".join("%f" % v for v in torch.cat(indices).cpu().numpy().astype(np.float64).mean(axis=0))
+                log(line)
             elif log is not None:
                 log("Epoch[%d] Train-total-loss=%f" % (epoch + 1, history[-1]))
             if epoch_end_callback is not None:

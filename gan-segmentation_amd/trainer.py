@@ -27,7 +27,9 @@ class DecoderTrainer:
     def __init__(self, cfg, params, device=0, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, seed=1,
                  dropout_keep=0.5, sync_bn=None, all_reduce=None, world=None, loss=None):
         """``loss``: None -- the reference's loss, ``train_ops.softmax_ce`` -- or a ``loss_ops.LossSpec`` (or a mapping of its keywords)
-        with numeric class weights: the step then calls ``loss_ops.softmax_loss`` and keeps its sums in ``last_sums``."""
+        with numeric class weights: the step then calls ``loss_ops.softmax_loss`` and keeps its sums in ``last_sums``.  A spec with a
+        ``region`` of weight > 0 adds weight times ``loss_ops.region_loss`` to that loss and accumulates its gradient into the
+        cross-entropy kernels' dlogits; ``last_region`` keeps the step's (n, classes) index tensor."""
         require_gpu()
         if not cfg["use_bn"]:
             raise NotImplementedError("training supports the reference's configuration: use_bn=True")
@@ -49,7 +51,8 @@ class DecoderTrainer:
         # the loss of loss_ops: class weights and the boundary table go to the device once
         self.loss = _loss_ops.check_spec(loss, "loss")
         self.last_sums = None       # (n, 4) float64 [W, B, S, T] of the last step with a spec; T / B is the reference's _k_sum
-        self._loss_cw = self._loss_table = self._loss_workspace = None
+        self.last_region = None     # (n, classes) float32 TI_k of the last step with a region term
+        self._loss_cw = self._loss_table = self._loss_workspace = self._region_workspace = None
         if self.loss is not None:
             if self.loss.needs_masks:
                 raise ValueError("loss: class_weights %r must be numbers here (SegSolver.fit computes them from its masks)"
@@ -215,6 +218,16 @@ class DecoderTrainer:
             self._loss_workspace = torch.empty(need, device=self.dev, dtype=torch.uint8)
         loss, self.last_sums, dlogits = _loss_ops.softmax_loss(logits, lab, self.loss, class_weights=self._loss_cw, dist2=dist2,
                                                                table=self._loss_table, workspace=self._loss_workspace)
+        region = self.loss.region
+        if region is not None and region["weight"] > 0:
+            # ce + weight * region; the region kernels add their gradient, scaled by the weight, to the one just written
+            need = _loss_ops.region_workspace_bytes(lab.shape[0], logits.shape[1], lab[0].numel())
+            if self._region_workspace is None or self._region_workspace.numel() < need:
+                self._region_workspace = torch.empty(need, device=self.dev, dtype=torch.uint8)
+            term, _sums, self.last_region, dlogits = _loss_ops.region_loss(
+                logits, lab, region["alpha"], region["beta"], region["smooth"], region["classes"], class_weights=self._loss_cw,
+                grad_scale=region["weight"], into=dlogits, workspace=self._region_workspace)
+            loss = loss + region["weight"] * term
         return loss, dlogits
 
     def _eye(self, C):
